@@ -26,9 +26,19 @@ max over ranks of the timed region, bracketed by barriers.
 
 Also reported: the roofline of the dominant kernel (c2: k_fill, HBM-bound,
 HIP events on the launch stream; c5: the whole step against its
-algorithmic bytes 12 B per row + 8 bitsets of G/8) and a CPU baseline (the
-oracle's restatement of lime's algorithm on a bounded sample), rank 0 /
-N = 1 only.
+algorithmic bytes 12 B per row + 8 bitsets of G/8), from the timed steps.
+
+A plain run sets up, warms up, times --steps steps, writes --dump-outputs
+and prints the line.  --full adds what takes runs of its own: a CPU
+baseline (the oracle's restatement of lime's algorithm on a bounded sample,
+rank 0 / N = 1 only) and, for c2, the short c3 / sub lines under
+'operators'.
+
+--dump-outputs DIR (N = 1, not --sharded): what the last timed step handed
+its caller, as DIR/<name>.npy (float64: the engine's u32 values are exact
+in it), at most 64 MB in all; outputs larger than their share are sampled at
+positions drawn from a fixed seed.  The inputs are synthetic from fixed
+seeds, so the same arguments give the same files from run to run.
 """
 import argparse
 import json
@@ -51,13 +61,21 @@ def parse():
                    help="c2: intersect + merge (the metric); c5: 8-way AND; c3: merge side "
                         "(sort + merge + carry + run ids + complement) of C3's pile-ups; sub: "
                         "subtract (lime mode) of the 1B-interval sets (2 x 5e8, len U[10,40])")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline figure does not need: the CPU "
+                        "baseline and (c2) the short c3 / sub lines under 'operators'")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last step's outputs as DIR/<name>.npy "
+                        "(float64, at most 64 MB in all, large outputs sampled at seeded "
+                        "positions); N = 1 without --sharded")
     p.add_argument("--no-ops", action="store_true",
-                   help="c2: skip the short c3 / sub lines reported under 'operators'")
+                   help="--full, c2: skip the short c3 / sub lines reported under 'operators'")
     p.add_argument("--ops-steps", type=int, default=3)
     p.add_argument("--rows", type=int, default=None,
                    help="rows per set (C2: 1e8; C5: 1.25e8, 8 sets)")
     p.add_argument("--chunk", type=int, default=1 << 31, help="pairs per output chunk")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--no-cpu-baseline", action="store_true",
+                   help="--full: skip the CPU baseline")
     p.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"])
     p.add_argument("--cpu-scale", type=int, default=100,
                    help="CPU sample: C2 density on hg38/scale with n/scale rows")
@@ -291,6 +309,9 @@ def spawn_ranks(n, script=None, argv=None):
 
 def main():
     args = parse()
+    if args.dump_outputs and (args.gpus > 1 or args.sharded):
+        sys.exit("bench.py: --dump-outputs writes the single-GPU step's outputs "
+                 "(--gpus 1, without --sharded)")
     if os.environ.get("LIME_BENCH_WATCHDOG"):  # debugging: every thread's stack, then exit
         import faulthandler
         faulthandler.dump_traceback_later(float(os.environ["LIME_BENCH_WATCHDOG"]), exit=True)
@@ -368,8 +389,12 @@ def main():
 
     benches = {"c2": bench_c2, "c5": bench_c5, "c3": bench_c3, "sub": bench_sub}
     step, finish = benches[args.workload](args, ctx, space, dev, world, rank, comm_dev, ev)
-    line = finish(measure(step, args.steps, args.warmup))
-    if args.workload == "c2" and not args.no_ops:
+    dt = measure(step, args.steps, args.warmup)
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        finish.dump(args.dump_outputs)
+    line = finish(dt)
+    if args.full and args.workload == "c2" and not args.no_ops:
         # the other operators north_star names, short lines at the same N
         # (the driver's scaling runs record them beside the metric)
         finish.release()
@@ -459,7 +484,42 @@ def bench_c2(args, ctx, space, dev, world, rank, comm_dev, ev):
             t.append(ev())
             state["phases"] = t
         state["npairs"], state["nruns"] = plan.n, ma.n + mb.n
+        if last_step and args.dump_outputs:
+            state["last"] = (plan, ma, mb, A, B)  # closed by dump(), after the timed region
+            return
         for h in (plan, ma, mb, A, B):
+            h.close()
+
+    def dump(d):
+        """The last step's outputs.  pairs: the 16-B records (start, end,
+        a_row, b_row) as they lie in the output buffer after the last fill:
+        with c chunks, the last chunk's k records at positions [0, k) and the
+        chunk before's at [k, chunk); pairs_index is each sampled record's
+        index among the plan's pairs.  merge_a / merge_b: the runs (global
+        start, end); merge_*_run_of_row: the run id of input row i (by its
+        original row number, so independent of the order of equal keys),
+        with the sampled i in *_index."""
+        import numpy as np
+        plan, ma, mb, A, B = state["last"]
+        total = plan.n
+        nch = max(1, -(-total // chunk))
+        k_last = total - (nch - 1) * chunk
+        pos = _sample(min(total, chunk), DUMP_PAIRS)
+        np.save(os.path.join(d, "pairs.npy"), _gather_u32(buf, pos))
+        np.save(os.path.join(d, "pairs_index.npy"),
+                (pos + np.where(pos < k_last, nch - 1, nch - 2) * chunk).astype(np.float64))
+        for name, mg in (("merge_a", ma), ("merge_b", mb)):
+            _dump_regions(d, name, mg, dev)
+            rid = torch.empty(m, dtype=torch.int32, device=dev)
+            row = torch.empty(m, dtype=torch.int32, device=dev)
+            mg.copy_run_ids_device(rid.data_ptr(), row.data_ptr())
+            of_row = torch.empty(m, dtype=torch.int32, device=dev)
+            of_row[row.to(torch.int64)] = rid
+            pos = _sample(m)
+            np.save(os.path.join(d, name + "_run_of_row.npy"), _gather_u32(of_row, pos))
+            np.save(os.path.join(d, name + "_run_of_row_index.npy"), pos.astype(np.float64))
+            del rid, row, of_row
+        for h in state.pop("last"):
             h.close()
 
     def finish(dt):
@@ -500,7 +560,7 @@ def bench_c2(args, ctx, space, dev, world, rank, comm_dev, ev):
             npairs, nruns = (int(x) for x in tt.tolist())
         traffic, tsrc = pmc_traffic("pmc_c2.json", "hbm_bytes_per_launch", world)
         cpu = None
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(args.cpu_scale, n)
         return {
             "metric": "intervals/sec for pairwise intersect+merge at 1/2/4/8 GPUs; "
@@ -532,6 +592,7 @@ def bench_c2(args, ctx, space, dev, world, rank, comm_dev, ev):
         buf = A_in = B_in = None
         torch.cuda.empty_cache()
     finish.release = release
+    finish.dump = dump
     return step, finish
 
 
@@ -563,7 +624,16 @@ def bench_c5(args, ctx, space, dev, world, rank, comm_dev, ev):
         if last_step:
             state["t"] = (t0, ev())
         state["runs"] = out["runs_total"]
+        if last_step and args.dump_outputs:
+            state["last"] = out["result"]  # closed by dump(), after the timed region
+            return
         out["result"].close()
+
+    def dump(d):
+        """the last step's runs of the k-way AND (global start, end)"""
+        res = state.pop("last")
+        _dump_regions(d, "and_runs", res, dev)
+        res.close()
 
     def finish(dt):
         ms = dt / args.steps * 1e3
@@ -572,7 +642,7 @@ def bench_c5(args, ctx, space, dev, world, rank, comm_dev, ev):
         alg = 12 * k * per + k * W  # rows read once + k bitsets (G/8 each)
         achieved = alg / world / (ms * 1e-3) / 1e9
         cpu = None
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
             cpu = c5_cpu_baseline(100, per)
         traffic, tsrc = pmc_traffic("pmc_c5.json", "hbm_bytes_per_step", world)
         return {
@@ -596,7 +666,47 @@ def bench_c5(args, ctx, space, dev, world, rank, comm_dev, ev):
                          "step_ms_hip_events": state["t"][0].elapsed_time(state["t"][1])},
             "cpu_baseline": cpu,
         }
+    finish.dump = dump
     return step, finish
+
+
+DUMP_SEED = 0xD0
+DUMP_PAIRS = 1 << 19  # sampled pair records: 2^19 x (4 + 1) float64 = 21 MB
+DUMP_ROWS = 1 << 18   # sampled positions of every other output: at most 6.3 MB each
+
+
+def _sample(n, k=DUMP_ROWS):
+    """every position of an n-long output if n <= k, else k positions drawn
+    with a fixed seed (sorted, duplicates dropped)"""
+    import numpy as np
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, k))
+
+
+def _gather_u32(t, pos):
+    """rows `pos` of a device int32 tensor that holds u32 values, as float64
+    on the host"""
+    import numpy as np
+    import torch
+    idx = torch.from_numpy(pos).to(t.device)
+    return t.index_select(0, idx).cpu().numpy().view(np.uint32).astype(np.float64)
+
+
+def _dump_regions(d, name, res, dev):
+    """a Result's regions (global start, end) as DIR/<name>.npy, shape (k, 2),
+    and their positions in the result as DIR/<name>_index.npy"""
+    import numpy as np
+    import torch
+    n = res.n
+    gs = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    ge = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    if n:
+        res.copy_rows_device(0, n, gs.data_ptr(), ge.data_ptr())
+    pos = _sample(n)
+    np.save(os.path.join(d, name + ".npy"),
+            np.stack([_gather_u32(gs, pos), _gather_u32(ge, pos)], 1))
+    np.save(os.path.join(d, name + "_index.npy"), pos.astype(np.float64))
 
 
 def pmc_traffic(name, field, world):
@@ -672,8 +782,11 @@ def bench_c3(args, ctx, space, dev, world, rank, comm_dev, ev, brief=False):
                 mg.copy_rows_device(0, k, rgs.data_ptr(), rge.data_ptr())
             gaps = ctx.complement_runs(space, k, rgs.data_ptr(), rge.data_ptr())
             runs, ng = mg.n, gaps.n
-            for h in (gaps, mg, S):
-                h.close()
+            if last_step and args.dump_outputs and not brief:
+                state["last"] = (gaps, mg, S)  # closed by dump(), after the timed region
+            else:
+                for h in (gaps, mg, S):
+                    h.close()
             del rgs, rge
         if last_step:
             state["t"] = (t0, ev())
@@ -706,10 +819,19 @@ def bench_c3(args, ctx, space, dev, world, rank, comm_dev, ev, brief=False):
                                    else "1 GPU"}})
         return out
 
+    def dump(d):
+        """the last step's merged runs and the complement's gaps (global start, end)"""
+        gaps, mg, S = state.pop("last")
+        _dump_regions(d, "merge_runs", mg, dev)
+        _dump_regions(d, "complement_gaps", gaps, dev)
+        for h in (gaps, mg, S):
+            h.close()
+
     def release():
         cols.clear()
         torch.cuda.empty_cache()
     finish.release = release
+    finish.dump = dump
     return step, finish
 
 
@@ -752,6 +874,16 @@ def bench_sub(args, ctx, space, dev, world, rank, comm_dev, ev, brief=False):
             res = ctx.subtract(A, B)
             hs = (res, A, B)
         state["records"] = res.n
+        if last_step and args.dump_outputs and not brief:
+            state["last"] = hs  # closed by dump(), after the timed region
+            return
+        for h in hs:
+            h.close()
+
+    def dump(d):
+        """the last step's remnant records (global start, end)"""
+        hs = state.pop("last")
+        _dump_regions(d, "subtract_records", hs[0], dev)
         for h in hs:
             h.close()
 
@@ -788,6 +920,7 @@ def bench_sub(args, ctx, space, dev, world, rank, comm_dev, ev, brief=False):
         B_in.clear()
         torch.cuda.empty_cache()
     finish.release = release
+    finish.dump = dump
     return step, finish
 
 

@@ -64,6 +64,15 @@ def test_spawn_ranks_wrong_world_reported(child):
     assert r.returncode != 0 and "n_gpus" in r.stderr
 
 
+def test_bench_refuses_dump_outputs_of_sharded_runs(tmp_path):
+    for extra in (["--gpus", "2"], ["--sharded"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dump-outputs",
+                            str(tmp_path / "out"), *extra],
+                           capture_output=True, text=True, timeout=120)
+        assert r.returncode != 0 and "--dump-outputs" in r.stderr
+        assert not (tmp_path / "out").exists()
+
+
 def test_bench_refuses_world_mismatch():
     env = dict(os.environ, WORLD_SIZE="2", RANK="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3"],

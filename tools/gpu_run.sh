@@ -5,7 +5,7 @@
 # steps:
 #   suite | suite:KEXPR   pytest -m gpu (optionally -k KEXPR)
 #   smoke                 __graft_entry__.smoke()
-#   bench:W               bench.py --workload W (the full line, CPU baseline included)
+#   bench:W               bench.py --full --workload W (the full line, CPU baseline included)
 #   rehearse:N            bench.py --gpus N --dist-backend gloo (its own N ranks sharing one GPU)
 #   prof:W                rocprofv3 --kernel-trace --stats of bench.py --workload W (c2 c5 c3 sub)
 #                         or of tools/bench_extra.py --workload W (anything else)
@@ -26,7 +26,7 @@ run() {  # name timeout cmd...
 }
 prog() {  # workload -> the python program + args that run it briefly
   case $1 in
-    c2) echo "bench.py --steps 5 --warmup 2 --no-cpu-baseline" ;;
+    c2) echo "bench.py --full --steps 5 --warmup 2 --no-cpu-baseline" ;;
     c5|c3|sub) echo "bench.py --workload $1 --steps 5 --warmup 2 --no-cpu-baseline" ;;
     *) echo "tools/bench_extra.py --workload $1" ;;
   esac
@@ -42,8 +42,8 @@ for S in "$@"; do
         run suite 1100 python -u -m pytest -v --timeout 600 --timeout-method thread -m gpu tests
       fi ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench_$a 500 python bench.py --workload $a ;;
-    rehearse) run rehearse_$a 1000 python bench.py --gpus $a --dist-backend gloo --steps 2 \
+    bench) run bench_$a 500 python bench.py --full --workload $a ;;
+    rehearse) run rehearse_$a 1000 python bench.py --full --gpus $a --dist-backend gloo --steps 2 \
                 --warmup 1 --ops-steps 2 ;;
     prof)
       run prof_$a 400 rocprofv3 --kernel-trace --stats --output-format csv \
