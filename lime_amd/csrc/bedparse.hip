@@ -21,7 +21,19 @@
 
 #include "common.hpp"
 
+// Owns its record arrays (pool blocks, released by the destructor).
 struct lime_dbed {
+    lime_dbed() = default;
+    lime_dbed(const lime_dbed &) = delete;
+    lime_dbed &operator=(const lime_dbed &) = delete;
+    ~lime_dbed() {
+        lime::release(ctx, contig);
+        lime::release(ctx, start);
+        lime::release(ctx, end);
+        lime::release(ctx, strand);
+        lime::release(ctx, name_off);
+        lime::release(ctx, name_len);
+    }
     lime_ctx *ctx = nullptr;
     int64_t n = 0;
     std::vector<std::string> names;
@@ -32,9 +44,9 @@ struct lime_dbed {
     uint32_t *name_len = nullptr;
     bool remapped = false;  // contig ids rewritten by lime_dbed_remap_contigs
 };
+static_assert(!std::is_copy_constructible<lime_dbed>::value, "lime_dbed owns pool blocks");
 
 namespace lime {
-void bed_free_device(lime_dbed *d);
 namespace {
 
 constexpr int PB = 256;
@@ -51,6 +63,15 @@ struct LineOut {
     uint32_t *name_len;
     int64_t *chrom_off;
     uint32_t *chrom_len;
+};
+
+// the record arrays of a lime_dbed, as k_emit writes them
+struct RecOut {
+    int32_t *contig;
+    uint32_t *start, *end;
+    int8_t *strand;
+    int64_t *name_off;
+    uint32_t *name_len;
 };
 
 __device__ __forceinline__ uint32_t count_nl16(uint4 v) {
@@ -241,7 +262,7 @@ __global__ __launch_bounds__(PB) void k_emit(const uint8_t *__restrict__ t, int6
                                              LineOut o, const uint32_t *__restrict__ rec,
                                              const int32_t *__restrict__ id_of_slot,
                                              const unsigned long long *__restrict__ hfirst,
-                                             lime_dbed out, unsigned long long *__restrict__ err) {
+                                             RecOut out, unsigned long long *__restrict__ err) {
     const int64_t j = (int64_t)blockIdx.x * PB + threadIdx.x;
     if (j >= lines || !o.flag[j]) return;
     const uint32_t slot = o.slot[j];
@@ -277,15 +298,14 @@ int bed_remap_device(lime_dbed *d, const int32_t *new_id, int32_t n_ids) {
     if (n_ids != (int32_t)d->names.size()) return fail(LIME_ERR_ARG, "remap table size != contigs");
     lime_ctx *ctx = d->ctx;
     if (d->n == 0 || n_ids == 0) return LIME_OK;
-    int32_t *dm;
-    LIME_TRY(alloc(ctx, &dm, (size_t)n_ids));
+    PoolPtr<int32_t> dm;
+    LIME_TRY(dm.alloc(ctx, (size_t)n_ids));
     LIME_HIP(hipMemcpyAsync(dm, new_id, sizeof(int32_t) * (size_t)n_ids, hipMemcpyHostToDevice,
                             S(ctx)));
     hipLaunchKernelGGL(k_remap, dim3(blocks_for(d->n, PB)), dim3(PB), 0, S(ctx), d->contig, d->n,
                        (const int32_t *)dm);
     LIME_HIP(hipGetLastError());
     LIME_HIP(hipStreamSynchronize(S(ctx)));
-    release(ctx, dm);
     d->remapped = true;
     return LIME_OK;
 }
@@ -293,15 +313,15 @@ int bed_remap_device(lime_dbed *d, const int32_t *new_id, int32_t n_ids) {
 // Parse `nbytes` of BED text held in host memory; the arrays stay in HBM.
 int bed_parse_device(lime_ctx *ctx, const char *text, int64_t nbytes, lime_dbed **out) {
     const unsigned long long none = ~0ull;
-    uint8_t *dt = nullptr;
-    LIME_TRY(alloc(ctx, &dt, (size_t)std::max<int64_t>(nbytes, 16)));
+    PoolPtr<uint8_t> dt;
+    LIME_TRY(dt.alloc(ctx, (size_t)std::max<int64_t>(nbytes, 16)));
     if (nbytes > 0)
         LIME_HIP(hipMemcpyAsync(dt, text, (size_t)nbytes, hipMemcpyHostToDevice, S(ctx)));
     const int64_t ntiles = std::max<int64_t>((nbytes + PTILE - 1) / PTILE, 1);
-    uint32_t *tcnt, *toff, *total;
-    LIME_TRY(alloc(ctx, &tcnt, (size_t)ntiles));
-    LIME_TRY(alloc(ctx, &toff, (size_t)ntiles));
-    LIME_TRY(alloc(ctx, &total, 1));
+    PoolPtr<uint32_t> tcnt, toff, total;
+    LIME_TRY(tcnt.alloc(ctx, (size_t)ntiles));
+    LIME_TRY(toff.alloc(ctx, (size_t)ntiles));
+    LIME_TRY(total.alloc(ctx, 1));
     hipLaunchKernelGGL(k_nl_count, dim3((unsigned)ntiles), dim3(PB), 0, S(ctx), dt, nbytes, tcnt);
     LIME_HIP(hipGetLastError());
     LIME_TRY(scan_exclusive_u32(ctx, tcnt, toff, ntiles, total));
@@ -310,25 +330,28 @@ int bed_parse_device(lime_ctx *ctx, const char *text, int64_t nbytes, lime_dbed 
     const bool tail = nbytes > 0 && text[nbytes - 1] != '\n';
     const int64_t lines = (int64_t)nl + (tail ? 1 : 0);
     const size_t L = (size_t)std::max<int64_t>(lines, 1);
-    int64_t *ls;
-    LIME_TRY(alloc(ctx, &ls, L + 1));
+    PoolPtr<int64_t> ls;
+    LIME_TRY(ls.alloc(ctx, L + 1));
     hipLaunchKernelGGL(k_nl_write, dim3((unsigned)ntiles), dim3(PB), 0, S(ctx), dt, nbytes,
                        (const uint32_t *)toff, ls);
     LIME_HIP(hipGetLastError());
-    LineOut o;
-    LIME_TRY(alloc(ctx, &o.flag, L));
-    LIME_TRY(alloc(ctx, &o.slot, L));
-    LIME_TRY(alloc(ctx, &o.start, L));
-    LIME_TRY(alloc(ctx, &o.end, L));
-    LIME_TRY(alloc(ctx, &o.strand, L));
-    LIME_TRY(alloc(ctx, &o.name_off, L));
-    LIME_TRY(alloc(ctx, &o.name_len, L));
-    LIME_TRY(alloc(ctx, &o.chrom_off, L));
-    LIME_TRY(alloc(ctx, &o.chrom_len, L));
-    unsigned long long *hkeys, *hfirst, *err;
-    LIME_TRY(alloc(ctx, &hkeys, HCAP));
-    LIME_TRY(alloc(ctx, &hfirst, HCAP));
-    LIME_TRY(alloc(ctx, &err, 4));
+    PoolPtr<uint32_t> flag, slot, lstart, lend, name_len, chrom_len;
+    PoolPtr<int8_t> lstrand;
+    PoolPtr<int64_t> name_off, chrom_off;
+    LIME_TRY(flag.alloc(ctx, L));
+    LIME_TRY(slot.alloc(ctx, L));
+    LIME_TRY(lstart.alloc(ctx, L));
+    LIME_TRY(lend.alloc(ctx, L));
+    LIME_TRY(lstrand.alloc(ctx, L));
+    LIME_TRY(name_off.alloc(ctx, L));
+    LIME_TRY(name_len.alloc(ctx, L));
+    LIME_TRY(chrom_off.alloc(ctx, L));
+    LIME_TRY(chrom_len.alloc(ctx, L));
+    const LineOut o{flag, slot, lstart, lend, lstrand, name_off, name_len, chrom_off, chrom_len};
+    PoolPtr<unsigned long long> hkeys, hfirst, err;
+    LIME_TRY(hkeys.alloc(ctx, HCAP));
+    LIME_TRY(hfirst.alloc(ctx, HCAP));
+    LIME_TRY(err.alloc(ctx, 4));
     LIME_HIP(hipMemsetAsync(hkeys, 0, sizeof(unsigned long long) * HCAP, S(ctx)));
     LIME_HIP(hipMemsetAsync(hfirst, 0xff, sizeof(unsigned long long) * HCAP, S(ctx)));
     LIME_HIP(hipMemsetAsync(err, 0xff, sizeof(unsigned long long) * 4, S(ctx)));
@@ -336,8 +359,8 @@ int bed_parse_device(lime_ctx *ctx, const char *text, int64_t nbytes, lime_dbed 
         hipLaunchKernelGGL(k_parse, dim3(blocks_for(lines, PB)), dim3(PB), 0, S(ctx), dt, nbytes,
                            (const int64_t *)ls, lines, (int64_t)nl, o, hkeys, hfirst, err);
     LIME_HIP(hipGetLastError());
-    uint32_t *rec;
-    LIME_TRY(alloc(ctx, &rec, L));
+    PoolPtr<uint32_t> rec;
+    LIME_TRY(rec.alloc(ctx, L));
     LIME_TRY(scan_exclusive_u32(ctx, o.flag, rec, lines, total));
     uint32_t nrec = 0;
     LIME_TRY(read_back(ctx, &nrec, total, sizeof(nrec)));
@@ -354,7 +377,7 @@ int bed_parse_device(lime_ctx *ctx, const char *text, int64_t nbytes, lime_dbed 
         rc = LIME_ERR_IO;
         msg = "too many distinct contig names";
     }
-    lime_dbed *d = new lime_dbed();
+    std::unique_ptr<lime_dbed> d(new lime_dbed());
     d->ctx = ctx;
     std::vector<int32_t> id_of_slot(HCAP, -1);
     if (rc == LIME_OK && nrec > 0) {
@@ -390,46 +413,27 @@ int bed_parse_device(lime_ctx *ctx, const char *text, int64_t nbytes, lime_dbed 
         LIME_TRY(alloc(ctx, &d->strand, R));
         LIME_TRY(alloc(ctx, &d->name_off, R));
         LIME_TRY(alloc(ctx, &d->name_len, R));
-        int32_t *dids;
-        LIME_TRY(alloc(ctx, &dids, HCAP));
+        PoolPtr<int32_t> dids;
+        LIME_TRY(dids.alloc(ctx, HCAP));
         LIME_HIP(hipMemcpyAsync(dids, id_of_slot.data(), sizeof(int32_t) * HCAP,
                                 hipMemcpyHostToDevice, S(ctx)));
         if (lines > 0)
             hipLaunchKernelGGL(k_emit, dim3(blocks_for(lines, PB)), dim3(PB), 0, S(ctx), dt,
                                lines, o, (const uint32_t *)rec, (const int32_t *)dids,
-                               (const unsigned long long *)hfirst, *d, err);
+                               (const unsigned long long *)hfirst,
+                               RecOut{d->contig, d->start, d->end, d->strand, d->name_off,
+                                      d->name_len},
+                               err);
         LIME_HIP(hipGetLastError());
         LIME_TRY(read_back(ctx, e, err, sizeof(e)));
         if (e[3] != none) {
             rc = LIME_ERR_IO;
             msg = "line " + std::to_string(e[3] + 1) + ": contig name hash collision";
         }
-        release(ctx, dids);
     }
-    for (void *p : {(void *)dt, (void *)tcnt, (void *)toff, (void *)total, (void *)ls,
-                    (void *)o.flag, (void *)o.slot, (void *)o.start, (void *)o.end,
-                    (void *)o.strand, (void *)o.name_off, (void *)o.name_len,
-                    (void *)o.chrom_off, (void *)o.chrom_len, (void *)hkeys, (void *)hfirst,
-                    (void *)err, (void *)rec})
-        ctx->pool.put(p);
-    if (rc != LIME_OK) {
-        bed_free_device(d);
-        return fail(rc, msg);
-    }
-    *out = d;
+    if (rc != LIME_OK) return fail(rc, msg);
+    *out = d.release();
     return LIME_OK;
-}
-
-void bed_free_device(lime_dbed *d) {
-    if (!d) return;
-    lime_ctx *ctx = d->ctx;
-    release(ctx, d->contig);
-    release(ctx, d->start);
-    release(ctx, d->end);
-    release(ctx, d->strand);
-    release(ctx, d->name_off);
-    release(ctx, d->name_len);
-    delete d;
 }
 
 }  // namespace lime
@@ -493,6 +497,6 @@ int lime_dbed_remap_contigs(lime_dbed *d, const int32_t *new_id_of_contig, int32
     return lime::bed_remap_device(d, new_id_of_contig, n);
 }
 
-void lime_dbed_free(lime_dbed *d) { lime::bed_free_device(d); }
+void lime_dbed_free(lime_dbed *d) { delete d; }
 
 }  // extern "C"

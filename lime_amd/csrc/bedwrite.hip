@@ -155,13 +155,13 @@ int format_bed(lime_ctx *ctx, const std::vector<uint32_t> &off,
         cat += s;
         noff.push_back((uint32_t)cat.size());
     }
-    uint32_t *d_off, *d_noff;
-    char *d_names;
-    uint64_t *len;
-    LIME_TRY(alloc(ctx, &d_off, off.size()));
-    LIME_TRY(alloc(ctx, &d_noff, noff.size()));
-    LIME_TRY(alloc(ctx, &d_names, std::max<size_t>(cat.size(), 1)));
-    LIME_TRY(alloc(ctx, &len, (size_t)std::max<int64_t>(n, 1)));
+    PoolPtr<uint32_t> d_off, d_noff;
+    PoolPtr<char> d_names;
+    PoolPtr<uint64_t> len;
+    LIME_TRY(d_off.alloc(ctx, off.size()));
+    LIME_TRY(d_noff.alloc(ctx, noff.size()));
+    LIME_TRY(d_names.alloc(ctx, std::max<size_t>(cat.size(), 1)));
+    LIME_TRY(len.alloc(ctx, (size_t)std::max<int64_t>(n, 1)));
     LIME_HIP(hipMemcpyAsync(d_off, off.data(), 4 * off.size(), hipMemcpyHostToDevice, S(ctx)));
     LIME_HIP(hipMemcpyAsync(d_noff, noff.data(), 4 * noff.size(), hipMemcpyHostToDevice, S(ctx)));
     if (!cat.empty())
@@ -171,29 +171,22 @@ int format_bed(lime_ctx *ctx, const std::vector<uint32_t> &off,
     if (n > 0) {
         hipLaunchKernelGGL(k_fmt_len, dim3(blocks_for(n, WB)), dim3(WB), 0, S(ctx), a, len);
         LIME_HIP(hipGetLastError());
-        uint64_t *tot;
-        LIME_TRY(alloc(ctx, &tot, 1));
+        PoolPtr<uint64_t> tot;
+        LIME_TRY(tot.alloc(ctx, 1));
         LIME_TRY(scan_exclusive_u64(ctx, len, len, n, tot));
         LIME_TRY(read_back(ctx, &total, tot, sizeof(total)));
-        release(ctx, tot);
     }
     *total_len = (int64_t)total;
-    int rc = LIME_OK;
     if (out && cap >= (int64_t)total && total > 0) {
-        char *d_out;
-        LIME_TRY(alloc(ctx, &d_out, (size_t)total));
+        PoolPtr<char> d_out;
+        LIME_TRY(d_out.alloc(ctx, (size_t)total));
         hipLaunchKernelGGL(k_fmt_write, dim3(blocks_for(n, WB)), dim3(WB), 0, S(ctx), a,
                            (const uint64_t *)len, total, d_out);
         LIME_HIP(hipGetLastError());
         LIME_HIP(hipMemcpyAsync(out, d_out, (size_t)total, hipMemcpyDeviceToHost, S(ctx)));
         LIME_HIP(hipStreamSynchronize(S(ctx)));
-        release(ctx, d_out);
     }
-    release(ctx, d_off);
-    release(ctx, d_noff);
-    release(ctx, d_names);
-    release(ctx, len);
-    return rc;
+    return LIME_OK;
 }
 
 }  // namespace lime

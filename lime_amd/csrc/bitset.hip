@@ -1474,8 +1474,6 @@ __global__ __launch_bounds__(256) void k_ev_join(const uint32_t *__restrict__ tc
     skip1[t] = jp;
 }
 
-int merge_runs(lime_ctx *ctx, const lime_set *set, lime_result *res, bool want_run_ids);
-
 int bitset_build(lime_ctx *ctx, const lime_set *a, lime_bitset *bs) {
     lime_result runs;
     runs.ctx = ctx;
@@ -1491,27 +1489,10 @@ int bitset_build(lime_ctx *ctx, const lime_set *a, lime_bitset *bs) {
         hipLaunchKernelGGL(k_paint, dim3((unsigned)nt), dim3(BB), 0, S(ctx), runs.gs, runs.ge,
                            runs.n, bs->words, bs->n_words);
     LIME_HIP(hipGetLastError());
-    release(ctx, runs.gs);
-    release(ctx, runs.ge);
     return LIME_OK;
 }
 
 namespace {
-// pool blocks released on every return path (a set of PoolGuards)
-struct PoolBag {
-    lime_ctx *ctx;
-    std::vector<void *> ps;
-    template <typename T>
-    int get(T **p, size_t count) {
-        LIME_TRY(alloc(ctx, p, count));
-        ps.push_back((void *)*p);
-        return LIME_OK;
-    }
-    ~PoolBag() {
-        for (void *p : ps) release(ctx, p);
-    }
-};
-
 int rows_error(unsigned int e) {
     if (e & 1u) return fail(LIME_ERR_CONTIG, "interval contig id outside the space");
     if (e & 2u) return fail(LIME_ERR_RANGE, "interval end < start");
@@ -1580,13 +1561,12 @@ int bin_rows(lime_ctx *ctx, const lime_space *sp, int64_t n, const int32_t *d_co
     if (getenv("LIME_TRACE_BINNING"))  // (read per call: tests set it at run time)
         fprintf(stderr, "lime: bin_rows n=%lld %s (rows per region %.0f, slots %u)\n",
                 (long long)n, rcap ? "optimistic" : "counted", E, rcap);
-    PoolBag bag{ctx, {}};
-    uint32_t *mat, *slab, *dummy, *gsum, *gpre;
-    LIME_TRY(bag.get(&mat, rcap ? 1 : (size_t)mlen));
-    LIME_TRY(bag.get(&slab, rcap ? (size_t)nb * nch * rcap : (size_t)std::max<int64_t>(n, 1)));
-    LIME_TRY(bag.get(&dummy, 64));
-    LIME_TRY(bag.get(&gsum, (size_t)ng * (size_t)nt));
-    LIME_TRY(bag.get(&gpre, (size_t)nt * (size_t)ng));
+    PoolPtr<uint32_t> mat, slab, dummy, gsum, gpre;
+    LIME_TRY(mat.alloc(ctx, rcap ? 1 : (size_t)mlen));
+    LIME_TRY(slab.alloc(ctx, rcap ? (size_t)nb * nch * rcap : (size_t)std::max<int64_t>(n, 1)));
+    LIME_TRY(dummy.alloc(ctx, 64));
+    LIME_TRY(gsum.alloc(ctx, (size_t)ng * (size_t)nt));
+    LIME_TRY(gpre.alloc(ctx, (size_t)nt * (size_t)ng));
     if (n == 0) {
         LIME_HIP(hipMemsetAsync(mat, 0, 4 * (size_t)mlen, S(ctx)));
         LIME_HIP(hipMemsetAsync(ttot, 0, 4 * ((size_t)nt + 1), S(ctx)));
@@ -1713,11 +1693,10 @@ int bin_set(lime_ctx *ctx, const lime_space *sp, int64_t n, const int32_t *d_con
             const uint32_t *d_len, int64_t lo, int64_t hi, int64_t nt, lime_bitset::Bins &b) {
     LIME_TRY(alloc(ctx, &b.tstart, (size_t)nt + 1));
     LIME_TRY(alloc(ctx, &b.slab2, (size_t)std::max<int64_t>(n, 1)));
-    PoolBag bag{ctx, {}};
-    uint64_t *cross;
-    unsigned int *flags;  // [0] ncross, [1] err (zeroed by k_bin_count)
-    LIME_TRY(bag.get(&cross, (size_t)std::max<int64_t>(2 * n, 1)));
-    LIME_TRY(bag.get(&flags, 2));
+    PoolPtr<uint64_t> cross;
+    PoolPtr<unsigned int> flags;  // [0] ncross, [1] err (zeroed by k_bin_count)
+    LIME_TRY(cross.alloc(ctx, (size_t)std::max<int64_t>(2 * n, 1)));
+    LIME_TRY(flags.alloc(ctx, 2));
     // the cross buckets allocated (and zeroed on the device) before the
     // read-back: after it only the bucketing launches remain
     LIME_TRY(alloc(ctx, &b.xb, 3 * ((size_t)nt + 1)));
@@ -1744,19 +1723,6 @@ int bin_set(lime_ctx *ctx, const lime_space *sp, int64_t n, const int32_t *d_con
 }
 }  // namespace
 
-void bitset_free(lime_bitset *bs) {
-    lime_ctx *ctx = bs->ctx;
-    release(ctx, bs->words);
-    bs->words = nullptr;
-    for (auto &b : bs->bins) {
-        release(ctx, b.slab2);
-        if (b.own_tstart) release(ctx, b.tstart);
-        release(ctx, b.xl);
-        release(ctx, b.xb);
-    }
-    bs->bins.clear();
-}
-
 // bits straight from UNSORTED device rows, no sort, no merge: the rows are
 // binned by paint tile (k_bin_count / k_bin_write / k_bin_split, their cross
 // pieces bucketed by tile) and kept so; the words are painted on first need
@@ -1782,9 +1748,8 @@ int bitset_paint(lime_ctx *ctx, const lime_bitset *cbs) {
     // painted into a local buffer, published only once every group has been
     // queued without error (a failed paint must not leave words that later
     // calls would take as valid)
-    uint64_t *words = nullptr;
-    LIME_TRY(alloc(ctx, &words, (size_t)std::max<int64_t>(bs->n_words, 1)));
-    PoolGuard<uint64_t> guard{ctx, words};
+    PoolPtr<uint64_t> words;
+    LIME_TRY(words.alloc(ctx, (size_t)std::max<int64_t>(bs->n_words, 1)));
     const int k = (int)bs->bins.size();
     for (int g0 = 0; g0 < k; g0 += MAXK) {
         std::vector<const lime_bitset::Bins *> b;
@@ -1796,8 +1761,7 @@ int bitset_paint(lime_ctx *ctx, const lime_bitset *cbs) {
             hipLaunchKernelGGL(k_paint_and, dim3((unsigned)bs->nt), dim3(PAINTB), 0, S(ctx), aa);
         LIME_HIP(hipGetLastError());
     }
-    bs->words = words;
-    guard.p = nullptr;  // (owned by the bitset from here)
+    bs->words = words.take();
     return LIME_OK;
 }
 
@@ -1805,13 +1769,7 @@ int bitset_paint(lime_ctx *ctx, const lime_bitset *cbs) {
 // then holds span / 8 bytes, and every op reads its words
 int bitset_drop_bins(lime_ctx *ctx, lime_bitset *bs) {
     LIME_TRY(bitset_paint(ctx, bs));
-    for (auto &b : bs->bins) {
-        release(ctx, b.slab2);
-        if (b.own_tstart) release(ctx, b.tstart);
-        release(ctx, b.xl);
-        release(ctx, b.xb);
-    }
-    bs->bins.clear();
+    bs->drop_bins();
     return LIME_OK;
 }
 
@@ -1835,15 +1793,14 @@ int bitset_and_rows(lime_ctx *ctx, const lime_space *sp, int k, const int64_t *n
     const int64_t nt = n_bins(hi - lo) * PSUB;
     bs->nt = nt;
     bs->bins.resize(k);
-    PoolBag keep{ctx, {}};
     // two cross buffers: set q's rows are binned while set q - 1's cross
     // pieces are read back and bucketed, so the host waits on an event of set
     // q - 1 only and the stream never drains between sets
-    uint64_t *cross[2];
-    unsigned int *flags;
-    LIME_TRY(keep.get(&cross[0], (size_t)std::max<int64_t>(2 * nmax, 1)));
-    LIME_TRY(keep.get(&cross[1], (size_t)std::max<int64_t>(2 * nmax, 1)));
-    LIME_TRY(keep.get(&flags, 2 * (size_t)k));  // (zeroed per set by its k_bin_count)
+    PoolPtr<uint64_t> cross[2];
+    PoolPtr<unsigned int> flags;
+    LIME_TRY(cross[0].alloc(ctx, (size_t)std::max<int64_t>(2 * nmax, 1)));
+    LIME_TRY(cross[1].alloc(ctx, (size_t)std::max<int64_t>(2 * nmax, 1)));
+    LIME_TRY(flags.alloc(ctx, 2 * (size_t)k));  // (zeroed per set by its k_bin_count)
     // set q's (ncross, err) land in the upper half of the pinned scratch
     // (read_back uses the lower half)
     unsigned int *hflags = reinterpret_cast<unsigned int *>(static_cast<char *>(ctx->pinned) + 2048);
@@ -1858,10 +1815,9 @@ int bitset_and_rows(lime_ctx *ctx, const lime_space *sp, int k, const int64_t *n
         LIME_HIP(hipEventCreateWithFlags(&ev.e[j], hipEventDisableTiming));
     // every set's tile starts: one block (owned by set 0)
     const size_t tstride = (size_t)nt + 1;
-    uint32_t *ttot_all;
-    LIME_TRY(alloc(ctx, &ttot_all, tstride * (size_t)k));
-    bs->bins[0].tstart = ttot_all;
     for (int i = 1; i < k; ++i) bs->bins[i].own_tstart = false;
+    LIME_TRY(alloc(ctx, &bs->bins[0].tstart, tstride * (size_t)k));
+    uint32_t *const ttot_all = bs->bins[0].tstart;
     // bucket set q's cross pieces by tile (its flags were copied to the host
     // behind its binning; wait for that copy only)
     auto bucket = [&](int q) -> int {
@@ -1906,6 +1862,20 @@ int bitset_and_rows(lime_ctx *ctx, const lime_space *sp, int k, const int64_t *n
 }
 
 namespace {
+// the words a call painted lazily (bitset_paint) go back to the pool if the
+// call fails after painting them; keep() on success
+struct PaintScope {
+    std::vector<lime_bitset *> fresh;  // without words when the call began
+    PaintScope(int k, const lime_bitset *const *sets) {
+        for (int i = 0; i < k; ++i)
+            if (!sets[i]->words) fresh.push_back(const_cast<lime_bitset *>(sets[i]));
+    }
+    void keep() { fresh.clear(); }
+    ~PaintScope() {
+        for (lime_bitset *b : fresh) release(b->ctx, b->words);
+    }
+};
+
 // op's runs over binned operands (sets[0..nin)), fused with their paint:
 // k_paint_ev, k_ev_join, a scan, k_ev_gather.  *overflow: a tile had more
 // events than its slot (the caller paints the operands and takes the words
@@ -1917,10 +1887,9 @@ struct EvPlan {
     lime_ctx *ctx;
     PaintEvArgs pa;
     int64_t nt = 0, cap = 0, bound = -1, rcap = -1;
-    uint32_t *cnt2 = nullptr, *skip1 = nullptr, *toff = nullptr;
-    unsigned int *hdr = nullptr;  // [0] overflow flag, [1] total events
-    PoolBag bag;
-    explicit EvPlan(lime_ctx *c) : ctx(c), bag{c, {}} {}
+    PoolPtr<uint32_t> tev, tcnt, edge, cnt2, skip1, toff;
+    PoolPtr<unsigned int> hdr;  // [0] overflow flag, [1] total events
+    explicit EvPlan(lime_ctx *c) : ctx(c) {}
 
     int prepare(int op, int nin, const lime_bitset *const *sets, uint32_t neg) {
         const lime_bitset *a = sets[0];
@@ -1944,13 +1913,16 @@ struct EvPlan {
         cap = bound < 0 ? 16384 : 2 * (2 * bound / std::max<int64_t>(nt, 1)) + 2048;
         cap = std::min<int64_t>(std::max<int64_t>((cap + 255) / 256 * 256, 4096), EVSLOT_MAX);
         pa.cap = (uint32_t)cap;
-        LIME_TRY(bag.get(&pa.tev, (size_t)nt * (size_t)cap));
-        LIME_TRY(bag.get(&pa.tcnt, (size_t)nt));
-        LIME_TRY(bag.get(&pa.edge, (size_t)nt));
-        LIME_TRY(bag.get(&cnt2, (size_t)nt));
-        LIME_TRY(bag.get(&skip1, (size_t)nt));
-        LIME_TRY(bag.get(&toff, (size_t)nt));
-        LIME_TRY(bag.get(&hdr, 2));  // [0] zeroed by k_paint_ev, [1] the scan's total
+        LIME_TRY(tev.alloc(ctx, (size_t)nt * (size_t)cap));
+        LIME_TRY(tcnt.alloc(ctx, (size_t)nt));
+        LIME_TRY(edge.alloc(ctx, (size_t)nt));
+        LIME_TRY(cnt2.alloc(ctx, (size_t)nt));
+        LIME_TRY(skip1.alloc(ctx, (size_t)nt));
+        LIME_TRY(toff.alloc(ctx, (size_t)nt));
+        LIME_TRY(hdr.alloc(ctx, 2));  // [0] zeroed by k_paint_ev, [1] the scan's total
+        pa.tev = tev;
+        pa.tcnt = tcnt;
+        pa.edge = edge;
         pa.oflow = hdr;
         return LIME_OK;
     }
@@ -1985,9 +1957,8 @@ struct EvPlan {
         LIME_TRY(read_back(ctx, h, hdr, sizeof(h)));
         if (h[0]) {
             if (rcap >= 0) {
-                release(ctx, res->gs);
+                release(ctx, res->gs);  // (the words path sizes the result again)
                 release(ctx, res->ge);
-                res->gs = res->ge = nullptr;
             }
             *overflow = true;
             return LIME_OK;
@@ -2050,13 +2021,13 @@ int bitset_runs(lime_ctx *ctx, int op, int k, const lime_bitset *const *sets, li
         LIME_TRY(runs_binned(ctx, op, nin, sets, res, &overflow));
         if (!overflow) return LIME_OK;
     }
+    PaintScope painted(nin, sets);
     for (int i = 0; i < nin; ++i) LIME_TRY(bitset_paint(ctx, sets[i]));
     // an AND of more than MAXK bitsets: their words ANDed group by group into
     // a temporary bitset, whose runs are then extracted (op 0)
-    uint64_t *tmp = nullptr;
-    PoolGuard<uint64_t> gt{ctx, tmp};
+    PoolPtr<uint64_t> tmp;
     if (op == 4 && k > MAXK) {
-        LIME_TRY(alloc(ctx, &tmp, (size_t)std::max<int64_t>(a->n_words, 1)));
+        LIME_TRY(tmp.alloc(ctx, (size_t)std::max<int64_t>(a->n_words, 1)));
         for (int g0 = 0; g0 < k; g0 += MAXK) {
             WordsAnd wa;
             wa.k = std::min(MAXK, k - g0);
@@ -2093,22 +2064,19 @@ int bitset_runs(lime_ctx *ctx, int op, int k, const lime_bitset *const *sets, li
         LIME_TRY(alloc(ctx, &res->gs, 1));
         LIME_TRY(alloc(ctx, &res->ge, 1));
         res->n = 0;
+        painted.keep();
         return LIME_OK;
     }
     // per-tile event slots + scan + gather (no look-back): C4's two
     // extractions 0.61 -> 0.43 ms against a one-pass decoupled look-back
     {
         const int64_t ntl = a->n_words / EV_TW + 1;
-        uint32_t *tev, *tcnt, *toff;
-        unsigned int *hdr;  // [0] overflow flag, [1] total events
-        LIME_TRY(alloc(ctx, &tev, (size_t)ntl * EVCAP));
-        PoolGuard<uint32_t> g0{ctx, tev};
-        LIME_TRY(alloc(ctx, &tcnt, (size_t)ntl));
-        PoolGuard<uint32_t> g1{ctx, tcnt};
-        LIME_TRY(alloc(ctx, &toff, (size_t)ntl));
-        PoolGuard<uint32_t> g2{ctx, toff};
-        LIME_TRY(alloc(ctx, &hdr, 2));
-        PoolGuard<unsigned int> g3{ctx, hdr};
+        PoolPtr<uint32_t> tev, tcnt, toff;
+        PoolPtr<unsigned int> hdr;  // [0] overflow flag, [1] total events
+        LIME_TRY(tev.alloc(ctx, (size_t)ntl * EVCAP));
+        LIME_TRY(tcnt.alloc(ctx, (size_t)ntl));
+        LIME_TRY(toff.alloc(ctx, (size_t)ntl));
+        LIME_TRY(hdr.alloc(ctx, 2));
         LIME_HIP(hipMemsetAsync(hdr, 0, 8, S(ctx)));
         hipLaunchKernelGGL(k_ev_local, dim3((unsigned)ntl), dim3(EV_NT), 0, S(ctx), oa, tev, tcnt,
                            hdr);
@@ -2140,6 +2108,7 @@ int bitset_runs(lime_ctx *ctx, int op, int k, const lime_bitset *const *sets, li
             if (cap >= 0) {
                 if (nr > cap) return fail(LIME_ERR_DEVICE, "bitset run extraction: runs past bound");
                 res->n = nr;
+                painted.keep();
                 return LIME_OK;
             }
             LIME_TRY(alloc(ctx, &res->gs, (size_t)std::max<int64_t>(nr, 1)));
@@ -2151,19 +2120,19 @@ int bitset_runs(lime_ctx *ctx, int op, int k, const lime_bitset *const *sets, li
                                    (uint32_t)h[1], res->gs, res->ge);
             LIME_HIP(hipGetLastError());
             res->n = nr;
+            painted.keep();
             return LIME_OK;
         }
         // a tile past EVCAP events: the two-pass path below
         if (cap >= 0) {
             release(ctx, res->gs);
             release(ctx, res->ge);
-            res->gs = res->ge = nullptr;
         }
     }
-    uint32_t *tcnt, *toff, *total;
-    LIME_TRY(alloc(ctx, &tcnt, (size_t)nt));
-    LIME_TRY(alloc(ctx, &toff, (size_t)nt));
-    LIME_TRY(alloc(ctx, &total, 1));
+    PoolPtr<uint32_t> tcnt, toff, total;
+    LIME_TRY(tcnt.alloc(ctx, (size_t)nt));
+    LIME_TRY(toff.alloc(ctx, (size_t)nt));
+    LIME_TRY(total.alloc(ctx, 1));
     hipLaunchKernelGGL(k_ev_count, dim3((unsigned)nt), dim3(BB), 0, S(ctx), oa, tcnt);
     LIME_HIP(hipGetLastError());
     LIME_TRY(scan_exclusive_u32(ctx, tcnt, toff, nt, total));
@@ -2176,17 +2145,16 @@ int bitset_runs(lime_ctx *ctx, int op, int k, const lime_bitset *const *sets, li
     hipLaunchKernelGGL(k_ev_write, dim3((unsigned)nt), dim3(BB), 0, S(ctx), oa,
                        (const uint32_t *)toff, res->gs, res->ge);
     LIME_HIP(hipGetLastError());
-    release(ctx, tcnt);
-    release(ctx, toff);
-    release(ctx, total);
     res->n = nr;
+    painted.keep();
     return LIME_OK;
 }
 
 int64_t bitset_popcount(lime_ctx *ctx, const lime_bitset *a) {
+    PaintScope painted(1, &a);
     if (bitset_paint(ctx, a) != LIME_OK) return -1;
-    unsigned long long *d;
-    if (alloc(ctx, &d, 1)) return -1;
+    PoolPtr<unsigned long long> d;
+    if (d.alloc(ctx, 1)) return -1;
     if (hipMemsetAsync(d, 0, 8, S(ctx)) != hipSuccess) return -1;
     unsigned grid = blocks_for(a->n_words, BB);
     if (grid > 8192) grid = 8192;
@@ -2194,7 +2162,7 @@ int64_t bitset_popcount(lime_ctx *ctx, const lime_bitset *a) {
     hipLaunchKernelGGL(k_popcount, dim3(grid), dim3(BB), 0, S(ctx), a->words, a->n_words, d);
     unsigned long long h = 0;
     if (read_back(ctx, &h, d, 8)) return -1;
-    release(ctx, d);
+    painted.keep();
     return (int64_t)h;
 }
 

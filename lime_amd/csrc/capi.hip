@@ -20,6 +20,7 @@ int fail(int code, const std::string &msg) {
 }
 
 void *Pool::get(size_t bytes) {
+    if (fail_at && --fail_at == 0) return nullptr;  // (LIME_TEST_ALLOC_FAIL)
     bytes = (bytes + 255) & ~(size_t)255;
     const hipStream_t cur = stream ? *stream : nullptr;
     auto range = free_blocks.equal_range(bytes);
@@ -103,62 +104,6 @@ int read_back(lime_ctx *c, void *host, const void *dev, size_t bytes) {
     memcpy(host, c->pinned, bytes);
     return LIME_OK;
 }
-
-// defined in the kernel translation units
-struct PairsPlan;
-int intersect_plan(lime_ctx *ctx, const lime_set *A, const lime_set *B, int64_t threshold,
-                   int64_t a_own, int64_t b_own, PairsPlan **out, const lime_set *A_out = nullptr,
-                   int64_t reach = -1);
-int window_plan(lime_ctx *ctx, const lime_set *A, const lime_set *B, int64_t d, PairsPlan **out);
-int format_bed(lime_ctx *ctx, const std::vector<uint32_t> &off,
-               const std::vector<std::string> &names, int64_t n, const uint32_t *gs,
-               const uint32_t *ge, const uint32_t *extra, char *out, int64_t cap,
-               int64_t *total_len);
-struct ClosestPlan;
-int closest_plan(lime_ctx *ctx, const lime_set *A, const lime_set *B, int mode, bool alive_in,
-                 bool *alive_out, ClosestPlan **out);
-int closest_fill(ClosestPlan *pl, int64_t first, int64_t count, lime_pair *d_out);
-int closest_checksum(ClosestPlan *pl, uint64_t *sum, uint64_t *xr);
-void closest_free(ClosestPlan *pl);
-int64_t closest_total(const ClosestPlan *pl);
-int closest_rounds(const ClosestPlan *pl, bool *sequential);
-int intersect_fill(PairsPlan *pl, int64_t first, int64_t count, lime_pair *d_out);
-int intersect_checksum(PairsPlan *pl, uint64_t *sum, uint64_t *xr);
-void intersect_free(PairsPlan *pl);
-int64_t plan_total(const PairsPlan *pl);
-int merge_runs(lime_ctx *ctx, const lime_set *set, lime_result *res, bool want_run_ids);
-int subtract_run(lime_ctx *ctx, const lime_set *A, const lime_set *B, int64_t threshold, int mode,
-                 lime_result *res);
-int complement_run(lime_ctx *ctx, const lime_result *runs, const uint32_t *d_off,
-                   const uint32_t *d_len, int32_t nc, lime_result *res, uint32_t wlo = 0,
-                   uint32_t whi = 0xffffffffu);
-int bitset_build(lime_ctx *ctx, const lime_set *a, lime_bitset *bs);
-int bitset_build_rows(lime_ctx *ctx, const lime_space *sp, int64_t n, const int32_t *d_contig,
-                      const uint32_t *d_start, const uint32_t *d_end, const uint32_t *d_off,
-                      const uint32_t *d_len, int64_t lo, int64_t hi, lime_bitset *bs);
-int bitset_and_rows(lime_ctx *ctx, const lime_space *sp, int k, const int64_t *n,
-                    const int32_t *const *d_contig, const uint32_t *const *d_start,
-                    const uint32_t *const *d_end, const uint32_t *d_off, const uint32_t *d_len,
-                    int64_t lo, int64_t hi, lime_bitset *bs);
-int sample_starts(lime_ctx *ctx, const lime_space *sp, int64_t n, const int32_t *d_contig,
-                  const uint32_t *d_start, int32_t k, uint32_t *d_out);
-int route_rows(lime_ctx *ctx, const lime_space *sp, int64_t n, const int32_t *d_contig,
-               const uint32_t *d_start, const uint32_t *d_end, uint32_t row_base, int32_t nsh,
-               const uint32_t *splits, int clip, int64_t cap, uint32_t *d_gs, uint32_t *d_ge,
-               uint32_t *d_row, int64_t *counts, const int8_t *d_strand_in,
-               int8_t *d_strand_out, uint32_t *d_iv = nullptr, int32_t ik = 0);
-int deinterleave_u32(lime_ctx *ctx, int64_t n, int32_t k, const uint32_t *src, uint32_t *d0,
-                     uint32_t *d1, uint32_t *d2);
-int bitset_runs(lime_ctx *ctx, int op, int k, const lime_bitset *const *sets, lime_result *res);
-int64_t bitset_popcount(lime_ctx *ctx, const lime_bitset *a);
-void bitset_free(lime_bitset *bs);
-int bitset_drop_bins(lime_ctx *ctx, lime_bitset *bs);
-int synth(lime_ctx *ctx, const lime_space *sp, int kind, int64_t first, int64_t n, uint64_t seed,
-          uint32_t lo, uint32_t hi, int64_t n_centres, uint32_t sigma, int32_t *d_contig,
-          uint32_t *d_start, uint32_t *d_end);
-
-int sort_set_global(lime_ctx *ctx, lime_set *set, const uint32_t *d_gs, const uint32_t *d_ge,
-                    const uint32_t *d_row, const uint32_t *d_len);
 
 __global__ void k_set_lower_bound(const uint32_t *gs, int64_t n, uint32_t key, int64_t *out) {
     if (threadIdx.x == 0) *out = dev::lower_bound(gs, 0, n, key);
@@ -255,6 +200,45 @@ SpaceDev::~SpaceDev() {
     release(ctx, len);
 }
 
+}  // namespace lime
+
+lime_set::~lime_set() {
+    lime::release(ctx, gs);
+    lime::release(ctx, ge);
+    lime::release(ctx, row);
+    lime::release(ctx, pmax);
+    lime::release(ctx, strand_in);
+    lime::release(ctx, tie_gs);
+    lime::release(ctx, tie_ge);
+    lime::release(ctx, tie_row);
+}
+
+lime_result::~lime_result() {
+    lime::release(ctx, gs);
+    lime::release(ctx, ge);
+    lime::release(ctx, a_row);
+    lime::release(ctx, b_row);
+    lime::release(ctx, run_of_sorted);
+    lime::release(ctx, run_strand);
+}
+
+void lime_bitset::drop_bins() {
+    for (auto &b : bins) {
+        lime::release(ctx, b.slab2);
+        if (b.own_tstart) lime::release(ctx, b.tstart);
+        lime::release(ctx, b.xl);
+        lime::release(ctx, b.xb);
+    }
+    bins.clear();
+}
+
+lime_bitset::~lime_bitset() {
+    lime::release(ctx, words);
+    drop_bins();
+}
+
+namespace lime {
+
 int space_device(lime_ctx *ctx, const std::vector<uint32_t> &off, const uint32_t **d_off,
                  const uint32_t **d_len, std::shared_ptr<SpaceDev> *keep) {
     auto it = ctx->spaces.find(off);
@@ -292,8 +276,8 @@ static int upload_space(lime_ctx *ctx, const lime_space *sp, uint32_t **d_off, u
     return LIME_OK;
 }
 
-static lime_set *new_set(lime_ctx *ctx, const lime_space *sp, int64_t n) {
-    lime_set *s = new lime_set();
+static std::unique_ptr<lime_set> new_set(lime_ctx *ctx, const lime_space *sp, int64_t n) {
+    std::unique_ptr<lime_set> s(new lime_set());
     s->ctx = ctx;
     s->n = n;
     s->n_contigs = sp->n;
@@ -309,24 +293,19 @@ static int create_from_device(lime_ctx *ctx, const lime_space *sp, int64_t n,
                               const uint32_t *d_end, lime_set **out,
                               int8_t *d_strand = nullptr, int min_shift = 0,
                               bool strand_uniform = false) {
-    lime_set *s = new_set(ctx, sp, n);
+    std::unique_ptr<lime_set> s = new_set(ctx, sp, n);
     s->strand_in = d_strand;
     s->strand_uniform = strand_uniform;
     s->min_shift = min_shift;
     uint32_t *d_len = nullptr;
-    int rc = upload_space(ctx, sp, &s->d_off, &d_len, &s->space_keep);
-    if (rc == LIME_OK) rc = sort_set(ctx, s, d_contig, d_start, d_end, d_len);
-    if (rc != LIME_OK) {
-        release(ctx, s->strand_in);
-        delete s;
-        return rc;
-    }
-    *out = s;
+    LIME_TRY(upload_space(ctx, sp, &s->d_off, &d_len, &s->space_keep));
+    LIME_TRY(sort_set(ctx, s.get(), d_contig, d_start, d_end, d_len));
+    *out = s.release();
     return LIME_OK;
 }
 
-static lime_result *new_result(lime_ctx *ctx, const lime_set *like) {
-    lime_result *r = new lime_result();
+static std::unique_ptr<lime_result> new_result(lime_ctx *ctx, const lime_set *like) {
+    std::unique_ptr<lime_result> r(new lime_result());
     r->ctx = ctx;
     r->off = like->off;
     r->n_contigs = like->n_contigs;
@@ -395,6 +374,8 @@ int lime_ctx_create(int device, lime_ctx **out) {
     }
     c->stream = c->own_stream;
     c->pool.stream = &c->stream;
+    // test hook: this context's N-th pool allocation fails (once)
+    if (const char *v = getenv("LIME_TEST_ALLOC_FAIL")) c->pool.fail_at = atoll(v) > 0 ? atoll(v) : 0;
     *out = c;
     return LIME_OK;
 }
@@ -510,20 +491,20 @@ static int create_host(lime_ctx *ctx, const lime_space *sp, int64_t n, const int
         s32[i] = (uint32_t)start[i];
         e32[i] = (uint32_t)end[i];
     }
-    int32_t *dc;
-    uint32_t *ds, *de;
-    LIME_TRY(alloc(ctx, &dc, (size_t)n));
-    LIME_TRY(alloc(ctx, &ds, (size_t)n));
-    LIME_TRY(alloc(ctx, &de, (size_t)n));
+    PoolPtr<int32_t> dc;
+    PoolPtr<uint32_t> ds, de;
+    LIME_TRY(dc.alloc(ctx, (size_t)n));
+    LIME_TRY(ds.alloc(ctx, (size_t)n));
+    LIME_TRY(de.alloc(ctx, (size_t)n));
     if (n > 0) {
         LIME_HIP(hipMemcpyAsync(dc, contig, 4 * (size_t)n, hipMemcpyHostToDevice, S(ctx)));
         LIME_HIP(hipMemcpyAsync(ds, s32.data(), 4 * (size_t)n, hipMemcpyHostToDevice, S(ctx)));
         LIME_HIP(hipMemcpyAsync(de, e32.data(), 4 * (size_t)n, hipMemcpyHostToDevice, S(ctx)));
         LIME_HIP(hipStreamSynchronize(S(ctx)));
     }
-    int8_t *dst = nullptr;
+    PoolPtr<int8_t> dst;
     if (strand) {
-        LIME_TRY(alloc(ctx, &dst, (size_t)std::max<int64_t>(n, 1)));
+        LIME_TRY(dst.alloc(ctx, (size_t)std::max<int64_t>(n, 1)));
         if (n > 0) {
             LIME_HIP(hipMemcpyAsync(dst, strand, (size_t)n, hipMemcpyHostToDevice, S(ctx)));
             LIME_HIP(hipStreamSynchronize(S(ctx)));
@@ -531,11 +512,7 @@ static int create_host(lime_ctx *ctx, const lime_space *sp, int64_t n, const int
     }
     bool uniform = true;
     for (int64_t i = 1; strand && i < n && uniform; ++i) uniform = strand[i] == strand[0];
-    int rc = create_from_device(ctx, sp, n, dc, ds, de, out, dst, 0, strand && uniform);
-    release(ctx, dc);
-    release(ctx, ds);
-    release(ctx, de);
-    return rc;
+    return create_from_device(ctx, sp, n, dc, ds, de, out, dst.take(), 0, strand && uniform);
 }
 
 int lime_set_create_device(lime_ctx *ctx, const lime_space *sp, int64_t n, const int32_t *d_contig,
@@ -555,29 +532,19 @@ int lime_set_create_device_stranded(lime_ctx *ctx, const lime_space *sp, int64_t
         return fail(LIME_ERR_ARG, "bad set arguments");
     if (n > 0xffffffffLL) return fail(LIME_ERR_RANGE, "more than 2^32 rows in one set");
     hipSetDevice(ctx->device);
-    int8_t *dst;  // the set keeps its own copy of the codes
-    LIME_TRY(alloc(ctx, &dst, (size_t)std::max<int64_t>(n, 1)));
+    PoolPtr<int8_t> dst;  // the set keeps its own copy of the codes
+    LIME_TRY(dst.alloc(ctx, (size_t)std::max<int64_t>(n, 1)));
     if (n > 0) {
         if (d_strand)
             LIME_HIP(hipMemcpyAsync(dst, d_strand, (size_t)n, hipMemcpyDeviceToDevice, S(ctx)));
         else
             LIME_HIP(hipMemsetAsync(dst, 0, (size_t)n, S(ctx)));
     }
-    return create_from_device(ctx, sp, n, d_contig, d_start, d_end, out, dst, 0, !d_strand);
+    return create_from_device(ctx, sp, n, d_contig, d_start, d_end, out, dst.take(), 0,
+                              !d_strand);
 }
 
 int lime_set_destroy(lime_set *s) {
-    if (!s) return LIME_OK;
-    lime_ctx *ctx = s->ctx;
-    release(ctx, s->gs);
-    release(ctx, s->ge);
-    release(ctx, s->row);
-    // (s->d_off is the context's cached space array: held by s->space_keep)
-    release(ctx, s->pmax);
-    release(ctx, s->strand_in);
-    release(ctx, s->tie_gs);
-    release(ctx, s->tie_ge);
-    release(ctx, s->tie_row);
     delete s;
     return LIME_OK;
 }
@@ -645,7 +612,7 @@ static int concat_sorted(lime_ctx *ctx, const lime_set *set, int64_t nl, const u
     const int64_t m = nl + set->n + nr, added = nl + nr;
     if (m > 0xffffffffLL) return fail(LIME_ERR_RANGE, "more than 2^32 rows in one set");
     hipSetDevice(ctx->device);
-    lime_set *s = new lime_set();
+    std::unique_ptr<lime_set> s(new lime_set());
     s->ctx = ctx;
     s->n = m;
     s->n_contigs = set->n_contigs;
@@ -661,13 +628,9 @@ static int concat_sorted(lime_ctx *ctx, const lime_set *set, int64_t nl, const u
         s->max_width = std::max(s->max_width, max_width);
         s->has_zero_width = s->has_zero_width || has_zero_width != 0;
     }
-    int rc = alloc(ctx, &s->gs, (size_t)std::max<int64_t>(m, 1));
-    if (rc == LIME_OK) rc = alloc(ctx, &s->ge, (size_t)std::max<int64_t>(m, 1));
-    if (rc == LIME_OK) rc = alloc(ctx, &s->row, (size_t)std::max<int64_t>(m, 1));
-    if (rc != LIME_OK) {
-        lime_set_destroy(s);
-        return rc;
-    }
+    LIME_TRY(alloc(ctx, &s->gs, (size_t)std::max<int64_t>(m, 1)));
+    LIME_TRY(alloc(ctx, &s->ge, (size_t)std::max<int64_t>(m, 1)));
+    LIME_TRY(alloc(ctx, &s->row, (size_t)std::max<int64_t>(m, 1)));
     hipError_t e = hipSuccess;
     auto part = [&](int64_t at, int64_t cnt, const uint32_t *g, const uint32_t *x,
                     const uint32_t *r) {
@@ -680,10 +643,8 @@ static int concat_sorted(lime_ctx *ctx, const lime_set *set, int64_t nl, const u
     part(0, nl, l_gs, l_ge, l_row);
     part(nl, set->n, set->gs, set->ge, set->row);
     part(nl + set->n, nr, r_gs, r_ge, r_row);
-    if (e != hipSuccess) {
-        lime_set_destroy(s);
+    if (e != hipSuccess)
         return fail(LIME_ERR_DEVICE, std::string("lime_set_extend_sorted copy: ") + hipGetErrorString(e));
-    }
     static const bool check = [] {
         const char *v = getenv("LIME_CHECK_EXTEND");
         return v && v[0] && v[0] != '0';
@@ -691,25 +652,20 @@ static int concat_sorted(lime_ctx *ctx, const lime_set *set, int64_t nl, const u
     if (check && added > 0) {
         // one pass over the whole new set: order everywhere, and the width
         // bounds over the added rows (the set's own rows are canonical)
-        unsigned int *err = nullptr, herr = 0;
-        rc = alloc(ctx, &err, 1);
-        if (rc == LIME_OK && hipMemsetAsync(err, 0, 4, S(ctx)) != hipSuccess) rc = LIME_ERR_DEVICE;
-        if (rc == LIME_OK) {
-            hipLaunchKernelGGL(k_check_join, dim3(blocks_for(m, 256)), dim3(256), 0, S(ctx), s->gs,
-                               s->ge, m, nl, nl + set->n, min_width, max_width,
-                               has_zero_width ? 1 : 0, err);
-            rc = read_back(ctx, &herr, err, sizeof(herr));
-        }
-        release(ctx, err);
-        if (rc == LIME_OK && herr) rc = fail(LIME_ERR_ARG, herr & 1u ? "extend: rows out of canonical order"
-                                                          : herr & 2u ? "extend: a width outside the bounds"
-                                                                      : "extend: a zero-width row without the flag");
-        if (rc != LIME_OK) {
-            lime_set_destroy(s);
-            return rc;
-        }
+        PoolPtr<unsigned int> err;
+        unsigned int herr = 0;
+        LIME_TRY(err.alloc(ctx, 1));
+        LIME_HIP(hipMemsetAsync(err, 0, 4, S(ctx)));
+        hipLaunchKernelGGL(k_check_join, dim3(blocks_for(m, 256)), dim3(256), 0, S(ctx), s->gs,
+                           s->ge, m, nl, nl + set->n, min_width, max_width,
+                           has_zero_width ? 1 : 0, err.get());
+        LIME_TRY(read_back(ctx, &herr, err, sizeof(herr)));
+        if (herr)
+            return fail(LIME_ERR_ARG, herr & 1u   ? "extend: rows out of canonical order"
+                                      : herr & 2u ? "extend: a width outside the bounds"
+                                                  : "extend: a zero-width row without the flag");
     }
-    *out = s;
+    *out = s.release();
     return LIME_OK;
 }
 
@@ -735,15 +691,11 @@ int lime_set_create_global(lime_ctx *ctx, const lime_space *sp, int64_t n, const
         return fail(LIME_ERR_ARG, "bad set arguments");
     if (n > 0xffffffffLL) return fail(LIME_ERR_RANGE, "more than 2^32 rows in one set");
     hipSetDevice(ctx->device);
-    lime_set *s = new_set(ctx, sp, n);
+    std::unique_ptr<lime_set> s = new_set(ctx, sp, n);
     uint32_t *d_len = nullptr;
-    int rc = upload_space(ctx, sp, &s->d_off, &d_len, &s->space_keep);
-    if (rc == LIME_OK) rc = sort_set_global(ctx, s, d_gs, d_ge, d_row, d_len);
-    if (rc != LIME_OK) {
-        delete s;
-        return rc;
-    }
-    *out = s;
+    LIME_TRY(upload_space(ctx, sp, &s->d_off, &d_len, &s->space_keep));
+    LIME_TRY(sort_set_global(ctx, s.get(), d_gs, d_ge, d_row, d_len));
+    *out = s.release();
     return LIME_OK;
 }
 
@@ -774,45 +726,41 @@ int lime_set_create_global_stranded(lime_ctx *ctx, const lime_space *sp, int64_t
     // sorted with positions as the row ids (so the strand pass and the
     // merge's strand lookups index the caller's codes), then the caller's row
     // ids and the codes gathered per sorted row
-    uint32_t *pos;
-    int8_t *st;
-    LIME_TRY(alloc(ctx, &pos, (size_t)std::max<int64_t>(n, 1)));
-    PoolGuard<uint32_t> g0{ctx, pos};
-    LIME_TRY(alloc(ctx, &st, (size_t)std::max<int64_t>(n, 1)));
+    PoolPtr<uint32_t> pos;
+    PoolPtr<int8_t> st;
+    LIME_TRY(pos.alloc(ctx, (size_t)std::max<int64_t>(n, 1)));
+    LIME_TRY(st.alloc(ctx, (size_t)std::max<int64_t>(n, 1)));
     if (n > 0) {
-        hipLaunchKernelGGL(k_positions, dim3(blocks_for(n, 256)), dim3(256), 0, S(ctx), pos, n);
+        hipLaunchKernelGGL(k_positions, dim3(blocks_for(n, 256)), dim3(256), 0, S(ctx), pos.get(),
+                           n);
         if (d_strand)
             LIME_HIP(hipMemcpyAsync(st, d_strand, (size_t)n, hipMemcpyDeviceToDevice, S(ctx)));
         else
             LIME_HIP(hipMemsetAsync(st, 0, (size_t)n, S(ctx)));
     }
-    lime_set *s = new_set(ctx, sp, n);
-    s->strand_in = st;
+    std::unique_ptr<lime_set> s = new_set(ctx, sp, n);
+    s->strand_in = st.take();
     s->strand_uniform = !d_strand;
     uint32_t *d_len = nullptr;
-    int rc = upload_space(ctx, sp, &s->d_off, &d_len, &s->space_keep);
-    if (rc == LIME_OK) rc = sort_set_global(ctx, s, d_gs, d_ge, pos, d_len);
-    uint32_t *row = nullptr;
-    int8_t *sst = nullptr;
-    if (rc == LIME_OK) rc = alloc(ctx, &row, (size_t)std::max<int64_t>(n, 1));
-    if (rc == LIME_OK) rc = alloc(ctx, &sst, (size_t)std::max<int64_t>(n, 1));
-    if (rc == LIME_OK && n > 0) {
+    LIME_TRY(upload_space(ctx, sp, &s->d_off, &d_len, &s->space_keep));
+    LIME_TRY(sort_set_global(ctx, s.get(), d_gs, d_ge, pos, d_len));
+    PoolPtr<uint32_t> row;
+    PoolPtr<int8_t> sst;
+    LIME_TRY(row.alloc(ctx, (size_t)std::max<int64_t>(n, 1)));
+    LIME_TRY(sst.alloc(ctx, (size_t)std::max<int64_t>(n, 1)));
+    if (n > 0) {
         hipLaunchKernelGGL(k_rows_of_positions, dim3(blocks_for(n, 256)), dim3(256), 0, S(ctx),
-                           (const uint32_t *)s->row, d_row, (const int8_t *)st, row, sst, n);
-        if (hipGetLastError() != hipSuccess) rc = fail(LIME_ERR_DEVICE, "row gather failed");
+                           (const uint32_t *)s->row, d_row, (const int8_t *)s->strand_in,
+                           row.get(), sst.get(), n);
+        if (hipGetLastError() != hipSuccess) return fail(LIME_ERR_DEVICE, "row gather failed");
     }
-    if (rc != LIME_OK) {
-        release(ctx, row);
-        release(ctx, sst);
-        lime_set_destroy(s);
-        return rc;
-    }
+    // the gathered arrays replace the positions and the input-order codes
     release(ctx, s->row);
     release(ctx, s->strand_in);
-    s->row = row;
-    s->strand_in = sst;
+    s->row = row.take();
+    s->strand_in = sst.take();
     s->strand_sorted = true;
-    *out = s;
+    *out = s.release();
     return LIME_OK;
 }
 
@@ -820,9 +768,8 @@ int64_t lime_set_lower_bound(const lime_set *s, uint32_t gkey) {
     if (!s) return -(int64_t)fail(LIME_ERR_ARG, "set is null");
     lime_ctx *ctx = s->ctx;
     hipSetDevice(ctx->device);
-    int64_t *d = nullptr;
-    if (int rc = alloc(ctx, &d, 1)) return -(int64_t)rc;
-    PoolGuard<int64_t> guard{ctx, d};
+    PoolPtr<int64_t> d;
+    if (int rc = d.alloc(ctx, 1)) return -(int64_t)rc;
     hipLaunchKernelGGL(k_set_lower_bound, dim3(1), dim3(64), 0, S(ctx), (const uint32_t *)s->gs,
                        s->n, gkey, d);
     if (hipError_t e = hipGetLastError())
@@ -843,10 +790,10 @@ int64_t lime_set_first_reaching(const lime_set *s, uint32_t gkey) {
     lime_ctx *ctx = s->ctx;
     hipSetDevice(ctx->device);
     if (s->n == 0) return 0;
+    LazyScope lazy(s);
     if (int rc = build_prefix_max(ctx, s)) return -(int64_t)rc;
-    int64_t *d = nullptr;
-    if (int rc = alloc(ctx, &d, 1)) return -(int64_t)rc;
-    PoolGuard<int64_t> guard{ctx, d};
+    PoolPtr<int64_t> d;
+    if (int rc = d.alloc(ctx, 1)) return -(int64_t)rc;
     hipLaunchKernelGGL(k_first_reaching, dim3(1), dim3(64), 0, S(ctx), (const uint32_t *)s->pmax,
                        s->n, gkey, d);
     if (hipError_t e = hipGetLastError())
@@ -854,6 +801,7 @@ int64_t lime_set_first_reaching(const lime_set *s, uint32_t gkey) {
                                                    hipGetErrorString(e));
     int64_t h = -1;
     if (int rc = read_back(ctx, &h, d, 8)) return -(int64_t)rc;
+    lazy.keep();
     return h;
 }
 
@@ -875,19 +823,20 @@ static int set_bounds(const lime_set *s, int32_t k, const uint32_t *keys, int64_
         for (int i = 0; i < k; ++i) out[i] = 0;
         return LIME_OK;
     }
+    LazyScope lazy(s);
     if (reaching) LIME_TRY(build_prefix_max(ctx, s));
-    uint32_t *d_keys = nullptr;
-    int64_t *d_out = nullptr;
-    LIME_TRY(alloc(ctx, &d_keys, (size_t)k));
-    PoolGuard<uint32_t> g0{ctx, d_keys};
-    LIME_TRY(alloc(ctx, &d_out, (size_t)k));
-    PoolGuard<int64_t> g1{ctx, d_out};
+    PoolPtr<uint32_t> d_keys;
+    PoolPtr<int64_t> d_out;
+    LIME_TRY(d_keys.alloc(ctx, (size_t)k));
+    LIME_TRY(d_out.alloc(ctx, (size_t)k));
     LIME_HIP(hipMemcpyAsync(d_keys, keys, 4 * (size_t)k, hipMemcpyHostToDevice, S(ctx)));
     hipLaunchKernelGGL(k_bounds, dim3(blocks_for(k, 64)), dim3(64), 0, S(ctx),
                        (const uint32_t *)(reaching ? s->pmax : s->gs), s->n,
                        (const uint32_t *)d_keys, (int)k, reaching ? 1 : 0, d_out);
     LIME_HIP(hipGetLastError());
-    return read_back(ctx, out, d_out, 8 * (size_t)k);
+    LIME_TRY(read_back(ctx, out, d_out, 8 * (size_t)k));
+    lazy.keep();
+    return LIME_OK;
 }
 
 int lime_set_lower_bounds(const lime_set *s, int32_t k, const uint32_t *gkeys, int64_t *out) {
@@ -953,6 +902,14 @@ struct lime_pairs {
     PairsPlan *plan;
     lime_ctx *ctx;
     ClosestPlan *closest = nullptr;  // set instead of plan for lime_closest_count
+    lime_pairs(PairsPlan *p, lime_ctx *c, ClosestPlan *cl = nullptr)
+        : plan(p), ctx(c), closest(cl) {}
+    lime_pairs(const lime_pairs &) = delete;
+    lime_pairs &operator=(const lime_pairs &) = delete;
+    ~lime_pairs() {
+        if (closest) closest_free(closest);
+        if (plan) intersect_free(plan);
+    }
 };
 
 static int pairs_fill(lime_pairs *p, int64_t first, int64_t count, lime_pair *d_out) {
@@ -1019,9 +976,7 @@ int lime_closest_count_chained(lime_ctx *ctx, const lime_set *a, const lime_set 
     bool out_live = false;
     LIME_TRY(closest_plan(ctx, a, b, mode, alive_in != 0, &out_live, &cl));
     if (alive_out) *alive_out = out_live ? 1 : 0;
-    lime_pairs *p = new lime_pairs{nullptr, ctx};
-    p->closest = cl;
-    *plan = p;
+    *plan = new lime_pairs{nullptr, ctx, cl};
     if (n_pairs) *n_pairs = closest_total(cl);
     return LIME_OK;
 }
@@ -1046,9 +1001,8 @@ int lime_intersect_fill_host(lime_pairs *plan, int64_t first, int64_t count, lim
     lime_ctx *ctx = plan->ctx;
     hipSetDevice(ctx->device);
     const int64_t chunk = 1 << 24;
-    lime_pair *stage = nullptr;
-    LIME_TRY(alloc(ctx, &stage, (size_t)std::min(chunk, std::max(count, (int64_t)1))));
-    PoolGuard<lime_pair> guard{ctx, stage};  // released on every return path
+    PoolPtr<lime_pair> stage;
+    LIME_TRY(stage.alloc(ctx, (size_t)std::min(chunk, std::max(count, (int64_t)1))));
     for (int64_t f = 0; f < count; f += chunk) {
         const int64_t c = std::min(chunk, count - f);
         LIME_TRY(pairs_fill(plan, first + f, c, stage));
@@ -1071,9 +1025,8 @@ int lime_pairs_checksum_device(lime_ctx *ctx, const lime_pair *d_pairs, int64_t 
     if (!ctx || count < 0 || (count > 0 && !d_pairs) || !sum || !xr)
         return fail(LIME_ERR_ARG, "bad checksum arguments");
     hipSetDevice(ctx->device);
-    unsigned long long *d_out = nullptr;
-    LIME_TRY(alloc(ctx, &d_out, 2));
-    PoolGuard<unsigned long long> g{ctx, d_out};
+    PoolPtr<unsigned long long> d_out;
+    LIME_TRY(d_out.alloc(ctx, 2));
     LIME_HIP(hipMemsetAsync(d_out, 0, 16, S(ctx)));
     if (count > 0)
         hipLaunchKernelGGL(k_pairs_hash, dim3(std::min<unsigned>(blocks_for(count, 256), 8192u)),
@@ -1088,11 +1041,6 @@ int lime_pairs_checksum_device(lime_ctx *ctx, const lime_pair *d_pairs, int64_t 
 }
 
 int lime_pairs_destroy(lime_pairs *plan) {
-    if (!plan) return LIME_OK;
-    if (plan->closest)
-        closest_free(plan->closest);
-    else
-        intersect_free(plan->plan);
     delete plan;
     return LIME_OK;
 }
@@ -1102,15 +1050,11 @@ int lime_merge(lime_ctx *ctx, const lime_set *a, lime_result **out, int64_t *n_r
     if (!ctx || !a || !out) return fail(LIME_ERR_ARG, "bad merge arguments");
     LIME_TRY(same_ctx(ctx, a));
     hipSetDevice(ctx->device);
-    lime_result *r = new_result(ctx, a);
+    std::unique_ptr<lime_result> r = new_result(ctx, a);
     r->src = a;
-    int rc = merge_runs(ctx, a, r, true);
-    if (rc != LIME_OK) {
-        delete r;
-        return rc;
-    }
-    *out = r;
+    LIME_TRY(merge_runs(ctx, a, r.get(), true));
     if (n_runs) *n_runs = r->n;
+    *out = r.release();
     return LIME_OK;
 }
 
@@ -1123,14 +1067,10 @@ int lime_subtract(lime_ctx *ctx, const lime_set *a, const lime_set *b, int64_t t
     LIME_TRY(same_ctx(ctx, a));
     LIME_TRY(same_ctx(ctx, b));
     hipSetDevice(ctx->device);
-    lime_result *r = new_result(ctx, a);
-    int rc = subtract_run(ctx, a, b, threshold, mode, r);
-    if (rc != LIME_OK) {
-        delete r;
-        return rc;
-    }
-    *out = r;
+    std::unique_ptr<lime_result> r = new_result(ctx, a);
+    LIME_TRY(subtract_run(ctx, a, b, threshold, mode, r.get()));
     if (n) *n = r->n;
+    *out = r.release();
     return LIME_OK;
 }
 
@@ -1147,17 +1087,10 @@ int lime_complement(lime_ctx *ctx, const lime_space *genome, const lime_set *a, 
     uint32_t *d_len = nullptr;
     uint32_t *d_off = nullptr;
     LIME_TRY(upload_space(ctx, genome, &d_off, &d_len));
-    lime_result *r = new_result(ctx, a);
-    int rc = complement_run(ctx, &runs, d_off, d_len, genome->n, r);
-    release(ctx, runs.gs);
-    release(ctx, runs.ge);
-
-    if (rc != LIME_OK) {
-        delete r;
-        return rc;
-    }
-    *out = r;
+    std::unique_ptr<lime_result> r = new_result(ctx, a);
+    LIME_TRY(complement_run(ctx, &runs, d_off, d_len, genome->n, r.get()));
     if (n) *n = r->n;
+    *out = r.release();
     return LIME_OK;
 }
 
@@ -1175,19 +1108,17 @@ int lime_complement_runs(lime_ctx *ctx, const lime_space *genome, int64_t n, con
     runs.n = n;
     runs.gs = const_cast<uint32_t *>(d_gs);
     runs.ge = const_cast<uint32_t *>(d_ge);
-    lime_result *r = new lime_result();
+    std::unique_ptr<lime_result> r(new lime_result());
     r->ctx = ctx;
     r->off = genome->off;
     r->n_contigs = genome->n;
     const uint32_t whi = hi >= 0xffffffffLL ? 0xffffffffu : (uint32_t)hi;
-    int rc = complement_run(ctx, &runs, d_off, d_len, genome->n, r, (uint32_t)std::min<int64_t>(lo, whi), whi);
-    runs.gs = runs.ge = nullptr;
-    if (rc != LIME_OK) {
-        lime_result_destroy(r);
-        return rc;
-    }
-    *out = r;
+    int rc = complement_run(ctx, &runs, d_off, d_len, genome->n, r.get(),
+                            (uint32_t)std::min<int64_t>(lo, whi), whi);
+    runs.gs = runs.ge = nullptr;  // (the caller's)
+    LIME_TRY(rc);
     if (n_regions) *n_regions = r->n;
+    *out = r.release();
     return LIME_OK;
 }
 
@@ -1307,12 +1238,10 @@ int lime_result_checksum(const lime_result *r, uint64_t *reg_sum, uint64_t *reg_
     if (!r || !reg_sum || !reg_xor) return fail(LIME_ERR_ARG, "bad checksum arguments");
     lime_ctx *ctx = r->ctx;
     hipSetDevice(ctx->device);
-    uint32_t *d_off = nullptr;
-    unsigned long long *d_out = nullptr;
-    LIME_TRY(alloc(ctx, &d_off, (size_t)r->n_contigs + 1));
-    PoolGuard<uint32_t> g1{ctx, d_off};
-    LIME_TRY(alloc(ctx, &d_out, 4));
-    PoolGuard<unsigned long long> g2{ctx, d_out};
+    PoolPtr<uint32_t> d_off;
+    PoolPtr<unsigned long long> d_out;
+    LIME_TRY(d_off.alloc(ctx, (size_t)r->n_contigs + 1));
+    LIME_TRY(d_out.alloc(ctx, 4));
     LIME_HIP(hipMemcpyAsync(d_off, r->off.data(), 4 * ((size_t)r->n_contigs + 1),
                             hipMemcpyHostToDevice, S(ctx)));
     LIME_HIP(hipMemsetAsync(d_out, 0, 32, S(ctx)));
@@ -1339,34 +1268,31 @@ int lime_result_checksum(const lime_result *r, uint64_t *reg_sum, uint64_t *reg_
 }
 
 int lime_result_destroy(lime_result *r) {
-    if (!r) return LIME_OK;
-    lime_ctx *ctx = r->ctx;
-    release(ctx, r->gs);
-    release(ctx, r->ge);
-    release(ctx, r->a_row);
-    release(ctx, r->b_row);
-    release(ctx, r->run_of_sorted);
-    release(ctx, r->run_strand);
     delete r;
     return LIME_OK;
 }
 
 // ------------------------------------------------------------------ bitset
+static std::unique_ptr<lime_bitset> new_bitset(lime_ctx *ctx, const lime_space *sp) {
+    std::unique_ptr<lime_bitset> bs(new lime_bitset());
+    bs->ctx = ctx;
+    bs->n_contigs = sp->n;
+    bs->off = sp->off;
+    bs->len = sp->len;
+    return bs;
+}
+
 int lime_bitset_from_set(lime_ctx *ctx, const lime_set *a, lime_bitset **out) {
     if (!ctx || !a || !out) return fail(LIME_ERR_ARG, "bad bitset arguments");
     LIME_TRY(same_ctx(ctx, a));
     hipSetDevice(ctx->device);
-    lime_bitset *bs = new lime_bitset();
+    std::unique_ptr<lime_bitset> bs(new lime_bitset());
     bs->ctx = ctx;
     bs->n_contigs = a->n_contigs;
     bs->off = a->off;
     bs->len = a->len;
-    int rc = bitset_build(ctx, a, bs);
-    if (rc != LIME_OK) {
-        delete bs;
-        return rc;
-    }
-    *out = bs;
+    LIME_TRY(bitset_build(ctx, a, bs.get()));
+    *out = bs.release();
     return LIME_OK;
 }
 
@@ -1380,19 +1306,10 @@ int lime_bitset_from_device(lime_ctx *ctx, const lime_space *sp, int64_t n,
     // rows binned by tile in one counting scatter, painted tile by tile
     uint32_t *d_off = nullptr, *d_len = nullptr;
     LIME_TRY(upload_space(ctx, sp, &d_off, &d_len));  // (borrowed)
-    lime_bitset *bs = new lime_bitset();
-    bs->ctx = ctx;
-    bs->n_contigs = sp->n;
-    bs->off = sp->off;
-    bs->len = sp->len;
-    int rc = bitset_build_rows(ctx, sp, n, d_contig, d_start, d_end, d_off, d_len, 0, sp->span,
-                               bs);
-    if (rc != LIME_OK) {
-        bitset_free(bs);
-        delete bs;
-        return rc;
-    }
-    *out = bs;
+    std::unique_ptr<lime_bitset> bs = new_bitset(ctx, sp);
+    LIME_TRY(bitset_build_rows(ctx, sp, n, d_contig, d_start, d_end, d_off, d_len, 0, sp->span,
+                               bs.get()));
+    *out = bs.release();
     return LIME_OK;
 }
 
@@ -1405,18 +1322,10 @@ int lime_bitset_from_global(lime_ctx *ctx, const lime_space *sp, int64_t lo, int
         return fail(LIME_ERR_ARG, "window must satisfy 0 <= lo <= hi <= span, lo % 64 == 0");
     if (n > 0xffffffffLL) return fail(LIME_ERR_RANGE, "more than 2^32 rows in one set");
     hipSetDevice(ctx->device);
-    lime_bitset *bs = new lime_bitset();
-    bs->ctx = ctx;
-    bs->n_contigs = sp->n;
-    bs->off = sp->off;
-    bs->len = sp->len;
-    int rc = bitset_build_rows(ctx, sp, n, nullptr, d_gs, d_ge, nullptr, nullptr, lo, hi, bs);
-    if (rc != LIME_OK) {
-        bitset_free(bs);
-        delete bs;
-        return rc;
-    }
-    *out = bs;
+    std::unique_ptr<lime_bitset> bs = new_bitset(ctx, sp);
+    LIME_TRY(bitset_build_rows(ctx, sp, n, nullptr, d_gs, d_ge, nullptr, nullptr, lo, hi,
+                               bs.get()));
+    *out = bs.release();
     return LIME_OK;
 }
 
@@ -1439,19 +1348,10 @@ static int bitset_and_entry(lime_ctx *ctx, const lime_space *sp, int64_t lo, int
     std::vector<const int32_t *> contig(k, nullptr);
     if (!global)
         for (int i = 0; i < k; ++i) contig[i] = d_contig[i];
-    lime_bitset *bs = new lime_bitset();
-    bs->ctx = ctx;
-    bs->n_contigs = sp->n;
-    bs->off = sp->off;
-    bs->len = sp->len;
-    int rc = bitset_and_rows(ctx, sp, k, n, contig.data(), d_start, d_end, d_off, d_len, lo, hi,
-                             bs);
-    if (rc != LIME_OK) {
-        bitset_free(bs);
-        delete bs;
-        return rc;
-    }
-    *out = bs;
+    std::unique_ptr<lime_bitset> bs = new_bitset(ctx, sp);
+    LIME_TRY(bitset_and_rows(ctx, sp, k, n, contig.data(), d_start, d_end, d_off, d_len, lo, hi,
+                             bs.get()));
+    *out = bs.release();
     return LIME_OK;
 }
 
@@ -1521,8 +1421,8 @@ int lime_sample_starts(lime_ctx *ctx, const lime_space *sp, int64_t n, const int
     return sample_starts(ctx, sp, n, d_contig, d_start, k, d_out);
 }
 
-static lime_result *bitset_result(lime_ctx *ctx, const lime_bitset *b) {
-    lime_result *r = new lime_result();
+static std::unique_ptr<lime_result> bitset_result(lime_ctx *ctx, const lime_bitset *b) {
+    std::unique_ptr<lime_result> r(new lime_result());
     r->ctx = ctx;
     r->off = b->off;
     r->n_contigs = b->n_contigs;
@@ -1539,14 +1439,10 @@ int lime_bitset_runs(lime_ctx *ctx, int op, const lime_bitset *a, const lime_bit
         return fail(LIME_ERR_ARG, "bitset belongs to another context (one context per thread)");
     hipSetDevice(ctx->device);
     const lime_bitset *sets[2] = {a, b};
-    lime_result *r = bitset_result(ctx, a);
-    int rc = bitset_runs(ctx, op, b ? 2 : 1, sets, r);
-    if (rc != LIME_OK) {
-        delete r;
-        return rc;
-    }
-    *out = r;
+    std::unique_ptr<lime_result> r = bitset_result(ctx, a);
+    LIME_TRY(bitset_runs(ctx, op, b ? 2 : 1, sets, r.get()));
     if (n) *n = r->n;
+    *out = r.release();
     return LIME_OK;
 }
 
@@ -1562,14 +1458,10 @@ int lime_bitset_and_runs(lime_ctx *ctx, int k, const lime_bitset *const *sets, l
             return fail(LIME_ERR_ARG, "bitset belongs to another context (one context per thread)");
     }
     hipSetDevice(ctx->device);
-    lime_result *r = bitset_result(ctx, sets[0]);
-    int rc = bitset_runs(ctx, 4, k, sets, r);
-    if (rc != LIME_OK) {
-        delete r;
-        return rc;
-    }
-    *out = r;
+    std::unique_ptr<lime_result> r = bitset_result(ctx, sets[0]);
+    LIME_TRY(bitset_runs(ctx, 4, k, sets, r.get()));
     if (n) *n = r->n;
+    *out = r.release();
     return LIME_OK;
 }
 
@@ -1586,8 +1478,6 @@ int lime_bitset_drop_bins(lime_ctx *ctx, lime_bitset *bs) {
 }
 
 int lime_bitset_destroy(lime_bitset *bs) {
-    if (!bs) return LIME_OK;
-    bitset_free(bs);
     delete bs;
     return LIME_OK;
 }

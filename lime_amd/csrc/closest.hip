@@ -35,15 +35,28 @@
 // Output per left: every k in [p_i, j_i) with dist(L_i, R[k]) == D_i, in
 // index order (= cache order), as (L, (L.row, R.row)) records.
 #include <algorithm>
+#include <utility>
 
 #include "common.hpp"
 
 namespace lime {
 
-int sort_set_global(lime_ctx *ctx, lime_set *set, const uint32_t *d_gs, const uint32_t *d_ge,
-                    const uint32_t *d_row, const uint32_t *d_len);
-
+// Owns its pool blocks; A and B are the caller's.
 struct ClosestPlan {
+    ClosestPlan() = default;
+    ClosestPlan(const ClosestPlan &) = delete;
+    ClosestPlan &operator=(const ClosestPlan &) = delete;
+    ~ClosestPlan() {
+        release(ctx, jp);
+        release(ctx, pp);
+        release(ctx, dd);
+        release(ctx, off);
+        release(ctx, rb);
+        release(ctx, aa);
+        release(ctx, eg);
+        release(ctx, ek);
+        release(ctx, deg);
+    }
     lime_ctx *ctx = nullptr;
     const lime_set *A = nullptr, *B = nullptr;
     int64_t nl = 0;
@@ -63,6 +76,7 @@ struct ClosestPlan {
     bool alive_in = true;      // the sweep enters this space live (chained spaces)
     bool alive_out = true;     // ... and leaves it live
 };
+static_assert(!std::is_copy_constructible<ClosestPlan>::value, "ClosestPlan owns pool blocks");
 
 namespace {
 
@@ -677,20 +691,7 @@ __global__ __launch_bounds__(CB) void k_scan(Lefts L, Rights R, EndIndex E,
 
 }  // namespace
 
-void closest_free(ClosestPlan *pl) {
-    if (!pl) return;
-    lime_ctx *ctx = pl->ctx;
-    release(ctx, pl->jp);
-    release(ctx, pl->pp);
-    release(ctx, pl->dd);
-    release(ctx, pl->off);
-    release(ctx, pl->rb);
-    release(ctx, pl->aa);
-    release(ctx, pl->eg);
-    release(ctx, pl->ek);
-    release(ctx, pl->deg);
-    delete pl;
-}
+void closest_free(ClosestPlan *pl) { delete pl; }
 
 int64_t closest_total(const ClosestPlan *pl) { return pl->total; }
 int closest_rounds(const ClosestPlan *pl, bool *sequential) {
@@ -700,25 +701,9 @@ int closest_rounds(const ClosestPlan *pl, bool *sequential) {
 
 namespace {
 
-// Scratch buffers of one plan build, returned to the pool however it ends.
-struct Scratch {
-    lime_ctx *ctx;
-    std::vector<void *> held;
-    template <typename T>
-    int get(T **p, size_t n) {
-        LIME_TRY(alloc(ctx, p, n));
-        held.push_back(*p);
-        return LIME_OK;
-    }
-    ~Scratch() {
-        for (void *q : held) ctx->pool.put(q);
-    }
-};
-
 int plan_body(lime_ctx *ctx, const lime_set *A, const lime_set *B, int mode, ClosestPlan *pl) {
     const int64_t nl = A->n, nr = B->n;
     const int32_t nc = A->n_contigs;
-    Scratch sc{ctx, {}};
 #define CL_TRY LIME_TRY
     CL_TRY(alloc(ctx, &pl->rb, (size_t)nc + 1));
     CL_TRY(alloc(ctx, &pl->jp, (size_t)std::max<int64_t>(nl, 1)));
@@ -734,15 +719,17 @@ int plan_body(lime_ctx *ctx, const lime_set *A, const lime_set *B, int mode, Clo
     hipLaunchKernelGGL(k_bounds, dim3(blocks_for(nc + 1, CB)), dim3(CB), 0, S(ctx), B->gs, nr,
                        B->d_off, nc, pl->rb);
     LIME_HIP(hipGetLastError());
+    LazyScope lazy(B);
     CL_TRY(build_prefix_max(ctx, B));
     // right-side search levels
     const int64_t m1 = (nr + 63) / 64, m2 = (m1 + 63) / 64;
-    uint32_t *jag, *jmin1, *jmin2, *gmax1, *gmax2;
-    CL_TRY(sc.get(&jag, (size_t)std::max<int64_t>(nr, 1)));
-    CL_TRY(sc.get(&jmin1, (size_t)std::max<int64_t>(m1, 1)));
-    CL_TRY(sc.get(&jmin2, (size_t)std::max<int64_t>(m2, 1)));
-    CL_TRY(sc.get(&gmax1, (size_t)std::max<int64_t>(m1, 1)));
-    CL_TRY(sc.get(&gmax2, (size_t)std::max<int64_t>(m2, 1)));
+    // (every scratch block of the build lives to its end)
+    PoolPtr<uint32_t> jag, jmin1, jmin2, gmax1, gmax2, lastU, idx;
+    CL_TRY(jag.alloc(ctx, (size_t)std::max<int64_t>(nr, 1)));
+    CL_TRY(jmin1.alloc(ctx, (size_t)std::max<int64_t>(m1, 1)));
+    CL_TRY(jmin2.alloc(ctx, (size_t)std::max<int64_t>(m2, 1)));
+    CL_TRY(gmax1.alloc(ctx, (size_t)std::max<int64_t>(m1, 1)));
+    CL_TRY(gmax2.alloc(ctx, (size_t)std::max<int64_t>(m2, 1)));
     if (nr > 0) {
         hipLaunchKernelGGL(k_jags, dim3(blocks_for(nr, CB)), dim3(CB), 0, S(ctx), B->gs, B->ge,
                            nr, B->d_off, nc, jag);
@@ -758,9 +745,9 @@ int plan_body(lime_ctx *ctx, const lime_set *A, const lime_set *B, int mode, Clo
     }
     // coarse directories of the starts and of the prefix max of ends
     pl->nb = ((int64_t)B->off[nc] >> DSH) + 1;
-    uint32_t *dgs, *dpm;
-    CL_TRY(sc.get(&dgs, (size_t)pl->nb + 1));
-    CL_TRY(sc.get(&dpm, (size_t)pl->nb + 1));
+    PoolPtr<uint32_t> dgs, dpm;
+    CL_TRY(dgs.alloc(ctx, (size_t)pl->nb + 1));
+    CL_TRY(dpm.alloc(ctx, (size_t)pl->nb + 1));
     hipLaunchKernelGGL(k_dir, dim3(blocks_for(pl->nb + 1, CB)), dim3(CB), 0, S(ctx), B->gs, nr,
                        dgs, pl->nb);
     hipLaunchKernelGGL(k_dir, dim3(blocks_for(pl->nb + 1, CB)), dim3(CB), 0, S(ctx),
@@ -770,25 +757,26 @@ int plan_body(lime_ctx *ctx, const lime_set *A, const lime_set *B, int mode, Clo
              gmax1, gmax2, nr,     dgs,     dpm, pl->nb};
     Lefts L{A->gs, A->ge, A->row, nl, A->d_off, nc, pl->rb};
     // right pointer: stops, prefix max, stuck positions
-    uint32_t *Aa, *Nn, *U, *P, *p2;
-    unsigned long long *stuck;
-    uint8_t *live;
-    unsigned int *changed;
+    uint32_t *Aa;
+    PoolPtr<uint32_t> Nn, U, P, p2;
+    PoolPtr<unsigned long long> stuck;
+    PoolPtr<uint8_t> live;
+    PoolPtr<unsigned int> changed;
     CL_TRY(alloc(ctx, &pl->aa, (size_t)nl));
     Aa = pl->aa;
-    CL_TRY(sc.get(&Nn, (size_t)nl));
-    CL_TRY(sc.get(&U, (size_t)nl));
-    CL_TRY(sc.get(&P, (size_t)nl));
-    CL_TRY(sc.get(&p2, (size_t)nl));
-    CL_TRY(sc.get(&stuck, (size_t)nc));
-    CL_TRY(sc.get(&live, (size_t)nc));
-    CL_TRY(sc.get(&changed, 1));
+    CL_TRY(Nn.alloc(ctx, (size_t)nl));
+    CL_TRY(U.alloc(ctx, (size_t)nl));
+    CL_TRY(P.alloc(ctx, (size_t)nl));
+    CL_TRY(p2.alloc(ctx, (size_t)nl));
+    CL_TRY(stuck.alloc(ctx, (size_t)nc));
+    CL_TRY(live.alloc(ctx, (size_t)nc));
+    CL_TRY(changed.alloc(ctx, 1));
     const unsigned gl = blocks_for(nl, CB);
     hipLaunchKernelGGL(k_stops, dim3(gl), dim3(CB), 0, S(ctx), L, R, Aa, Nn);
     LIME_HIP(hipGetLastError());
     LIME_HIP(hipMemsetAsync(stuck, 0xff, sizeof(unsigned long long) * (size_t)nc, S(ctx)));
-    uint32_t *lbd;
-    CL_TRY(sc.get(&lbd, (size_t)nc + 1));
+    PoolPtr<uint32_t> lbd;
+    CL_TRY(lbd.alloc(ctx, (size_t)nc + 1));
     hipLaunchKernelGGL(k_bounds, dim3(blocks_for(nc + 1, CB)), dim3(CB), 0, S(ctx), A->gs, nl,
                        A->d_off, nc, lbd);
     LIME_HIP(hipGetLastError());
@@ -806,10 +794,9 @@ int plan_body(lime_ctx *ctx, const lime_set *A, const lime_set *B, int mode, Clo
     // left contig only from the end of this contig's rights, and only if no
     // rights lie on the contigs in between
     {
-        uint32_t *lastU;
-        CL_TRY(sc.get(&lastU, (size_t)nc));
+        CL_TRY(lastU.alloc(ctx, (size_t)nc));
         hipLaunchKernelGGL(k_last, dim3(blocks_for(nc, CB)), dim3(CB), 0, S(ctx),
-                           (const uint32_t *)lbd, (const uint32_t *)(mode == 0 ? U : pl->jp), nc,
+                           (const uint32_t *)lbd, (const uint32_t *)(mode == 0 ? U.get() : pl->jp), nc,
                            lastU);
         LIME_HIP(hipGetLastError());
         std::vector<uint32_t> rb(nc + 1), lb(nc + 1), lu(nc);
@@ -847,8 +834,7 @@ int plan_body(lime_ctx *ctx, const lime_set *A, const lime_set *B, int mode, Clo
     CL_TRY(alloc(ctx, &pl->eg, (size_t)std::max<int64_t>(nr, 1)));
     CL_TRY(alloc(ctx, &pl->ek, (size_t)std::max<int64_t>(nr, 1)));
     if (nr > 0) {
-        uint32_t *idx;
-        CL_TRY(sc.get(&idx, (size_t)nr));
+        CL_TRY(idx.alloc(ctx, (size_t)nr));
         hipLaunchKernelGGL(k_iota, dim3(blocks_for(nr, CB)), dim3(CB), 0, S(ctx), idx, nr);
         LIME_HIP(hipGetLastError());
         lime_set es;  // (ge, ge, k) sorted by ge; ties keep k ascending
@@ -861,8 +847,8 @@ int plan_body(lime_ctx *ctx, const lime_set *A, const lime_set *B, int mode, Clo
         CL_TRY(sort_set_global(ctx, &es, B->ge, B->ge, idx, nullptr));
         release(ctx, pl->eg);
         release(ctx, pl->ek);
-        pl->eg = es.gs;
-        pl->ek = es.row;
+        pl->eg = std::exchange(es.gs, nullptr);
+        pl->ek = std::exchange(es.row, nullptr);
         release(ctx, es.ge);
         CL_TRY(alloc(ctx, &pl->deg, (size_t)pl->nb + 1));
         hipLaunchKernelGGL(k_dir, dim3(blocks_for(pl->nb + 1, CB)), dim3(CB), 0, S(ctx),
@@ -911,9 +897,9 @@ int plan_body(lime_ctx *ctx, const lime_set *A, const lime_set *B, int mode, Clo
         LIME_HIP(hipGetLastError());
     }
     // output counts and offsets
-    uint64_t *cnt, *tot;
-    CL_TRY(sc.get(&cnt, (size_t)nl));
-    CL_TRY(sc.get(&tot, 1));
+    PoolPtr<uint64_t> cnt, tot;
+    CL_TRY(cnt.alloc(ctx, (size_t)nl));
+    CL_TRY(tot.alloc(ctx, 1));
     const EndIndex E{pl->eg, pl->ek, pl->aa, nr, pl->deg, pl->nb};
     hipLaunchKernelGGL(k_scan<SCAN_COUNT>, dim3(gl), dim3(CB), 0, S(ctx), L, R, E,
                        (const uint32_t *)pl->jp, (const uint32_t *)pl->pp,
@@ -926,6 +912,7 @@ int plan_body(lime_ctx *ctx, const lime_set *A, const lime_set *B, int mode, Clo
     uint64_t total = 0;
     LIME_TRY(read_back(ctx, &total, tot, sizeof(total)));
     pl->total = (int64_t)total;
+    lazy.keep();
 #undef CL_TRY
     return LIME_OK;
 }
@@ -936,19 +923,15 @@ int closest_plan(lime_ctx *ctx, const lime_set *A, const lime_set *B, int mode, 
                  bool *alive_out, ClosestPlan **out) {
     if (A->n >= (int64_t)NONE || B->n >= (int64_t)NONE)
         return fail(LIME_ERR_RANGE, "closest supports fewer than 2^32 - 1 rows per set");
-    ClosestPlan *pl = new ClosestPlan();
+    std::unique_ptr<ClosestPlan> pl(new ClosestPlan());
     pl->ctx = ctx;
     pl->A = A;
     pl->B = B;
     pl->nl = A->n;
     pl->alive_in = alive_in;
-    const int rc = plan_body(ctx, A, B, mode, pl);
-    if (rc != LIME_OK) {
-        closest_free(pl);
-        return rc;
-    }
+    LIME_TRY(plan_body(ctx, A, B, mode, pl.get()));
     if (alive_out) *alive_out = pl->alive_out;
-    *out = pl;
+    *out = pl.release();
     return LIME_OK;
 }
 
@@ -972,8 +955,8 @@ int closest_fill(ClosestPlan *pl, int64_t first, int64_t count, lime_pair *d_out
 
 int closest_checksum(ClosestPlan *pl, uint64_t *sum, uint64_t *xr) {
     lime_ctx *ctx = pl->ctx;
-    unsigned long long *ck;
-    LIME_TRY(alloc(ctx, &ck, 2));
+    PoolPtr<unsigned long long> ck;
+    LIME_TRY(ck.alloc(ctx, 2));
     LIME_HIP(hipMemsetAsync(ck, 0, 2 * sizeof(unsigned long long), S(ctx)));
     if (pl->nl > 0) {
         const lime_set *A = pl->A, *B = pl->B;
@@ -989,7 +972,6 @@ int closest_checksum(ClosestPlan *pl, uint64_t *sum, uint64_t *xr) {
     }
     unsigned long long h[2];
     LIME_TRY(read_back(ctx, h, ck, sizeof(h)));
-    release(ctx, ck);
     *sum = h[0];
     *xr = h[1];
     return LIME_OK;

@@ -12,6 +12,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/lime_amd.h"
@@ -57,6 +58,9 @@ struct Pool {
     bool multi_stream = false;
     int64_t held = 0;
     int64_t in_use = 0, peak = 0;  // bytes of live blocks; their high-water mark
+    // test hook (LIME_TEST_ALLOC_FAIL, read by lime_ctx_create): the get that
+    // returns null, counted down; 0: none
+    int64_t fail_at = 0;
     void *get(size_t bytes);
     void put(void *p);
     void release_all();
@@ -101,7 +105,12 @@ struct lime_space {
 };
 
 // Device-resident sorted set: canonical order (gstart, zero-width first).
+// Owns its pool blocks (released by the destructor); d_off is borrowed.
 struct lime_set {
+    lime_set() = default;
+    lime_set(const lime_set &) = delete;
+    lime_set &operator=(const lime_set &) = delete;
+    ~lime_set();
     lime_ctx *ctx = nullptr;
     int64_t n = 0;
     uint32_t *gs = nullptr;   // global start
@@ -138,7 +147,13 @@ struct lime_set {
     int min_shift = 0;
 };
 
+// Owns its pool blocks (released by the destructor); src and d_off are
+// borrowed.
 struct lime_result {
+    lime_result() = default;
+    lime_result(const lime_result &) = delete;
+    lime_result &operator=(const lime_result &) = delete;
+    ~lime_result();
     lime_ctx *ctx = nullptr;
     int64_t n = 0;
     uint32_t *gs = nullptr;   // global start
@@ -153,7 +168,15 @@ struct lime_result {
     std::vector<uint32_t> off;
 };
 
+// Owns its words and the blocks of its bins (released by the destructor);
+// d_off is borrowed.
 struct lime_bitset {
+    lime_bitset() = default;
+    lime_bitset(const lime_bitset &) = delete;
+    lime_bitset &operator=(const lime_bitset &) = delete;
+    ~lime_bitset();
+    // releases the bins' blocks (the words stay)
+    void drop_bins();
     lime_ctx *ctx = nullptr;
     uint64_t *words = nullptr;
     int64_t n_words = 0;
@@ -180,6 +203,10 @@ struct lime_bitset {
     int64_t nt = 0;  // paint tiles of the bins
 };
 
+static_assert(!std::is_copy_constructible<lime_set>::value, "lime_set owns pool blocks");
+static_assert(!std::is_copy_constructible<lime_result>::value, "lime_result owns pool blocks");
+static_assert(!std::is_copy_constructible<lime_bitset>::value, "lime_bitset owns pool blocks");
+
 namespace lime {
 
 inline hipStream_t S(lime_ctx *c) { return c->stream; }
@@ -199,12 +226,74 @@ inline void release(lime_ctx *c, T *&p) {
     p = nullptr;
 }
 
-// RAII release of a pool block on every return path
+// Owner of one pool block, move-only.  The block goes back to the pool when
+// the owner dies, unless it was released early (reset: a deliberate point --
+// a later allocation of the same rounded size reuses the block, so these
+// set the peak) or handed over (take: into a set / result field, or to a
+// caller).
 template <typename T>
-struct PoolGuard {
-    lime_ctx *ctx;
-    T *&p;
-    ~PoolGuard() { release(ctx, p); }
+class PoolPtr {
+  public:
+    PoolPtr() = default;
+    PoolPtr(lime_ctx *c, T *p) : ctx_(c), p_(p) {}  // adopts a block handed over
+    PoolPtr(PoolPtr &&o) noexcept : ctx_(o.ctx_), p_(o.take()) {}
+    PoolPtr &operator=(PoolPtr &&o) noexcept {
+        if (this != &o) {
+            reset();
+            ctx_ = o.ctx_;
+            p_ = o.take();
+        }
+        return *this;
+    }
+    PoolPtr(const PoolPtr &) = delete;
+    PoolPtr &operator=(const PoolPtr &) = delete;
+    ~PoolPtr() { reset(); }
+    int alloc(lime_ctx *c, size_t count) {
+        reset();
+        ctx_ = c;
+        return lime::alloc(c, &p_, count);
+    }
+    void reset() {
+        if (p_) release(ctx_, p_);
+    }
+    T *take() {
+        T *p = p_;
+        p_ = nullptr;
+        return p;
+    }
+    T *get() const { return p_; }
+    operator T *() const { return p_; }
+
+  private:
+    lime_ctx *ctx_ = nullptr;
+    T *p_ = nullptr;
+};
+
+// What a call builds lazily on a (const) set -- the prefix max, the tie index
+// -- goes back to the pool if the call fails after building it: a failed call
+// leaves the context's live bytes as it found them.  keep() on success.
+class LazyScope {
+  public:
+    explicit LazyScope(const lime_set *s)
+        : s_(s), had_pmax_(s->pmax != nullptr), had_tie_(s->tie_n >= 0) {}
+    LazyScope(const LazyScope &) = delete;
+    LazyScope &operator=(const LazyScope &) = delete;
+    void keep() { s_ = nullptr; }
+    ~LazyScope() {
+        if (!s_) return;
+        std::lock_guard<std::mutex> lock(s_->ctx->mu);
+        if (!had_pmax_) release(s_->ctx, s_->pmax);
+        if (!had_tie_) {
+            release(s_->ctx, s_->tie_gs);
+            release(s_->ctx, s_->tie_ge);
+            release(s_->ctx, s_->tie_row);
+            s_->tie_n = -1;
+        }
+    }
+
+  private:
+    const lime_set *s_;
+    const bool had_pmax_, had_tie_;
 };
 
 // read a device scalar back to the host (synchronises the context stream)
@@ -234,6 +323,63 @@ int scan_exclusive_u64(lime_ctx *ctx, const uint64_t *in, uint64_t *out, int64_t
 int build_prefix_max(lime_ctx *ctx, const lime_set *set);
 // inclusive prefix max of a u32 array (out may alias in)
 int prefix_max_u32(lime_ctx *ctx, const uint32_t *in, uint32_t *out, int64_t n);
+int sort_set_global(lime_ctx *ctx, lime_set *set, const uint32_t *d_gs, const uint32_t *d_ge,
+                    const uint32_t *d_row, const uint32_t *d_len);
+int merge_runs(lime_ctx *ctx, const lime_set *set, lime_result *res, bool want_run_ids);
+int merge_runs_with_pmax(lime_ctx *ctx, const lime_set *set, lime_result *res, int *tie_big);
+int subtract_run(lime_ctx *ctx, const lime_set *A, const lime_set *B, int64_t threshold, int mode,
+                 lime_result *res);
+int complement_run(lime_ctx *ctx, const lime_result *runs, const uint32_t *d_off,
+                   const uint32_t *d_len, int32_t nc, lime_result *res, uint32_t wlo = 0,
+                   uint32_t whi = 0xffffffffu);
+// pair plans (intersect.hip, closest.hip): owned by the caller, freed by
+// intersect_free / closest_free
+struct PairsPlan;
+struct ClosestPlan;
+int intersect_plan(lime_ctx *ctx, const lime_set *A, const lime_set *B, int64_t threshold,
+                   int64_t a_own, int64_t b_own, PairsPlan **out, const lime_set *A_out = nullptr,
+                   int64_t reach = -1);
+int window_plan(lime_ctx *ctx, const lime_set *A, const lime_set *B, int64_t d, PairsPlan **out);
+int owner_ranges(lime_ctx *ctx, const lime_set *O, const lime_set *P, int st, int64_t threshold,
+                 uint32_t *olo, uint32_t *ocnt);
+int intersect_fill(PairsPlan *pl, int64_t first, int64_t count, lime_pair *d_out);
+int intersect_checksum(PairsPlan *pl, uint64_t *sum, uint64_t *xr);
+void intersect_free(PairsPlan *pl);
+int64_t plan_total(const PairsPlan *pl);
+int closest_plan(lime_ctx *ctx, const lime_set *A, const lime_set *B, int mode, bool alive_in,
+                 bool *alive_out, ClosestPlan **out);
+int closest_fill(ClosestPlan *pl, int64_t first, int64_t count, lime_pair *d_out);
+int closest_checksum(ClosestPlan *pl, uint64_t *sum, uint64_t *xr);
+void closest_free(ClosestPlan *pl);
+int64_t closest_total(const ClosestPlan *pl);
+int closest_rounds(const ClosestPlan *pl, bool *sequential);
+int format_bed(lime_ctx *ctx, const std::vector<uint32_t> &off,
+               const std::vector<std::string> &names, int64_t n, const uint32_t *gs,
+               const uint32_t *ge, const uint32_t *extra, char *out, int64_t cap,
+               int64_t *total_len);
+int bitset_build(lime_ctx *ctx, const lime_set *a, lime_bitset *bs);
+int bitset_build_rows(lime_ctx *ctx, const lime_space *sp, int64_t n, const int32_t *d_contig,
+                      const uint32_t *d_start, const uint32_t *d_end, const uint32_t *d_off,
+                      const uint32_t *d_len, int64_t lo, int64_t hi, lime_bitset *bs);
+int bitset_and_rows(lime_ctx *ctx, const lime_space *sp, int k, const int64_t *n,
+                    const int32_t *const *d_contig, const uint32_t *const *d_start,
+                    const uint32_t *const *d_end, const uint32_t *d_off, const uint32_t *d_len,
+                    int64_t lo, int64_t hi, lime_bitset *bs);
+int bitset_runs(lime_ctx *ctx, int op, int k, const lime_bitset *const *sets, lime_result *res);
+int64_t bitset_popcount(lime_ctx *ctx, const lime_bitset *a);
+int bitset_drop_bins(lime_ctx *ctx, lime_bitset *bs);
+int sample_starts(lime_ctx *ctx, const lime_space *sp, int64_t n, const int32_t *d_contig,
+                  const uint32_t *d_start, int32_t k, uint32_t *d_out);
+int route_rows(lime_ctx *ctx, const lime_space *sp, int64_t n, const int32_t *d_contig,
+               const uint32_t *d_start, const uint32_t *d_end, uint32_t row_base, int32_t nsh,
+               const uint32_t *splits, int clip, int64_t cap, uint32_t *d_gs, uint32_t *d_ge,
+               uint32_t *d_row, int64_t *counts, const int8_t *d_strand_in,
+               int8_t *d_strand_out, uint32_t *d_iv = nullptr, int32_t ik = 0);
+int deinterleave_u32(lime_ctx *ctx, int64_t n, int32_t k, const uint32_t *src, uint32_t *d0,
+                     uint32_t *d1, uint32_t *d2);
+int synth(lime_ctx *ctx, const lime_space *sp, int kind, int64_t first, int64_t n, uint64_t seed,
+          uint32_t lo, uint32_t hi, int64_t n_centres, uint32_t sigma, int32_t *d_contig,
+          uint32_t *d_start, uint32_t *d_end);
 
 }  // namespace lime
 

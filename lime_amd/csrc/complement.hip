@@ -138,12 +138,12 @@ int complement_run(lime_ctx *ctx, const lime_result *runs, const uint32_t *d_off
     a.off = d_off;
     a.len = d_len;
     a.nc = nc;
-    uint32_t *cnt, *pre, *coff, *crb, *total;
-    LIME_TRY(alloc(ctx, &cnt, (size_t)nr + 1));
-    LIME_TRY(alloc(ctx, &pre, (size_t)nr + 1));
-    LIME_TRY(alloc(ctx, &coff, (size_t)nc + 1));
-    LIME_TRY(alloc(ctx, &crb, (size_t)nc + 1));
-    LIME_TRY(alloc(ctx, &total, 1));
+    PoolPtr<uint32_t> cnt, pre, coff, crb, total;
+    LIME_TRY(cnt.alloc(ctx, (size_t)nr + 1));
+    LIME_TRY(pre.alloc(ctx, (size_t)nr + 1));
+    LIME_TRY(coff.alloc(ctx, (size_t)nc + 1));
+    LIME_TRY(crb.alloc(ctx, (size_t)nc + 1));
+    LIME_TRY(total.alloc(ctx, 1));
     if (nr > 0)
         hipLaunchKernelGGL(k_gap_count, dim3(blocks_for(nr, CB)), dim3(CB), 0, S(ctx), a, cnt);
     LIME_TRY(scan_exclusive_u32(ctx, cnt, pre, nr, pre + nr));
@@ -160,11 +160,6 @@ int complement_run(lime_ctx *ctx, const lime_result *runs, const uint32_t *d_off
                            (const uint32_t *)pre, (const uint32_t *)coff, (const uint32_t *)crb,
                            res->gs, res->ge);
     LIME_HIP(hipGetLastError());
-    release(ctx, cnt);
-    release(ctx, pre);
-    release(ctx, coff);
-    release(ctx, crb);
-    release(ctx, total);
     res->n = n;
     return LIME_OK;
 }

@@ -34,7 +34,27 @@
 
 namespace lime {
 
+// a window plan's widened set: its row array is A's (borrowed), only gs / ge
+// are its own
+struct DropWidened {
+    void operator()(lime_set *w) const {
+        w->row = nullptr;
+        delete w;
+    }
+};
+
+// Owns its per-owner / per-tile pool blocks and W.
 struct PairsPlan {
+    PairsPlan() = default;
+    PairsPlan(const PairsPlan &) = delete;
+    PairsPlan &operator=(const PairsPlan &) = delete;
+    ~PairsPlan() {
+        release(ctx, olo);
+        release(ctx, ocnt);
+        release(ctx, toff);
+        release(ctx, win);
+        release(ctx, tseg);
+    }
     lime_ctx *ctx;
     const lime_set *A, *B;
     int64_t threshold;
@@ -51,11 +71,10 @@ struct PairsPlan {
     // window plans (DistributedWindow): A is the widened set W, A_out the
     // caller's set whose own coordinates the pairs carry; reach = distance
     const lime_set *A_out = nullptr;
-    lime_set *W = nullptr;  // owned: widened copy of A_out (row array borrowed)
+    std::unique_ptr<lime_set, DropWidened> W;  // widened copy of A_out
     int64_t reach = -1;
 };
-
-void intersect_free(PairsPlan *pl);
+static_assert(!std::is_copy_constructible<PairsPlan>::value, "PairsPlan owns pool blocks");
 
 namespace {
 
@@ -1038,7 +1057,7 @@ int intersect_plan(lime_ctx *ctx, const lime_set *A, const lime_set *B, int64_t 
                    int64_t reach) {
     if (a_own < 0 || a_own > A->n) a_own = A->n;
     if (b_own < 0 || b_own > B->n) b_own = B->n;
-    PairsPlan *pl = new PairsPlan();
+    std::unique_ptr<PairsPlan> pl(new PairsPlan());
     pl->ctx = ctx;
     pl->A = A;
     pl->B = B;
@@ -1053,16 +1072,14 @@ int intersect_plan(lime_ctx *ctx, const lime_set *A, const lime_set *B, int64_t 
     pl->nt0 = (a_own + OT - 1) / OT;
     pl->nt1 = (b_own + OT - 1) / OT;
     const int64_t nt = pl->nt0 + pl->nt1;
-    int rc = LIME_OK;
-    uint64_t *tcnt = nullptr, *total = nullptr;
-    if ((rc = alloc(ctx, &pl->olo, (size_t)(a_own + b_own))) ||
-        (rc = alloc(ctx, &pl->ocnt, (size_t)(a_own + b_own))) ||
-        (rc = alloc(ctx, &pl->toff, (size_t)nt)) || (rc = alloc(ctx, &pl->win, (size_t)2 * nt)) ||
-        (rc = alloc(ctx, &pl->tseg, (size_t)nt)) ||
-        (rc = alloc(ctx, &tcnt, (size_t)nt)) || (rc = alloc(ctx, &total, 2))) {
-        delete pl;
-        return rc;
-    }
+    PoolPtr<uint64_t> tcnt, total;
+    LIME_TRY(alloc(ctx, &pl->olo, (size_t)(a_own + b_own)));
+    LIME_TRY(alloc(ctx, &pl->ocnt, (size_t)(a_own + b_own)));
+    LIME_TRY(alloc(ctx, &pl->toff, (size_t)nt));
+    LIME_TRY(alloc(ctx, &pl->win, (size_t)2 * nt));
+    LIME_TRY(alloc(ctx, &pl->tseg, (size_t)nt));
+    LIME_TRY(tcnt.alloc(ctx, (size_t)nt));
+    LIME_TRY(total.alloc(ctx, 2));
     // total[1]: overflow flag of the u32 tile-local offsets
     uint32_t *oflow = reinterpret_cast<uint32_t *>(total + 1);
     LIME_HIP(hipMemsetAsync(total + 1, 0, sizeof(uint64_t), S(ctx)));
@@ -1099,18 +1116,14 @@ int intersect_plan(lime_ctx *ctx, const lime_set *A, const lime_set *B, int64_t 
     LIME_TRY(scan_exclusive_u64(ctx, tcnt, pl->toff, nt, total));
     uint64_t tot[2] = {0, 0};
     LIME_TRY(read_back(ctx, tot, total, sizeof(tot)));
-    release(ctx, tcnt);
-    release(ctx, total);
-    if (tot[1] & 1) {
-        intersect_free(pl);
+    if (tot[1] & 1)
         return fail(LIME_ERR_OVERFLOW,
                     "a tile of 1024 owner rows has 2^32 or more candidate pairs (pile-up)");
-    }
     pl->total = (int64_t)tot[0];
     // sparse plans commit two owner tiles per fill step (k_fill<2>) unless
     // a tile holds 2^31 or more pairs (two tiles' u32 offsets could wrap)
     pl->tpf = !(tot[1] & 2) && pl->total < (int64_t)LIME_FILL_SPARSE * (a_own + b_own) ? 2 : 1;
-    *out = pl;
+    *out = pl.release();
     return LIME_OK;
 }
 
@@ -1126,18 +1139,16 @@ int owner_ranges(lime_ctx *ctx, const lime_set *O, const lime_set *P, int st, in
     }
     const int64_t tp = threshold > 1 ? threshold : 1;
     const int64_t ntl = (O->n + OT - 1) / OT;
-    uint32_t *win;
-    uint64_t *tcnt;
-    LIME_TRY(alloc(ctx, &win, (size_t)2 * ntl));
-    LIME_TRY(alloc(ctx, &tcnt, (size_t)ntl));
+    PoolPtr<uint32_t> win;
+    PoolPtr<uint64_t> tcnt;
+    LIME_TRY(win.alloc(ctx, (size_t)2 * ntl));
+    LIME_TRY(tcnt.alloc(ctx, (size_t)ntl));
     StreamArgs sa = stream_args(O, P, st, threshold, 0, 0);
     launch_windows(ctx, sa, tp, ntl, (int64_t)O->max_width, win, nullptr, 0, nullptr);
     hipLaunchKernelGGL((k_count<false, false>), dim3((unsigned)ntl), dim3(IB), 0, S(ctx), sa, tp,
                        threshold,
                        (const uint32_t *)win, olo, ocnt, tcnt, (uint32_t *)nullptr);
     LIME_HIP(hipGetLastError());
-    release(ctx, win);
-    release(ctx, tcnt);
     return LIME_OK;
 }
 
@@ -1149,8 +1160,8 @@ int intersect_fill(PairsPlan *pl, int64_t first, int64_t count, lime_pair *d_out
 
 int intersect_checksum(PairsPlan *pl, uint64_t *sum, uint64_t *xr) {
     lime_ctx *ctx = pl->ctx;
-    uint64_t *ck;
-    LIME_TRY(alloc(ctx, &ck, 2));
+    PoolPtr<uint64_t> ck;
+    LIME_TRY(ck.alloc(ctx, 2));
     LIME_HIP(hipMemsetAsync(ck, 0, 16, S(ctx)));
     // bound each launch to keep the grid size in range
     const int64_t step = (int64_t)SBLK * 1048576;
@@ -1158,7 +1169,6 @@ int intersect_checksum(PairsPlan *pl, uint64_t *sum, uint64_t *xr) {
         LIME_TRY(launch_fill(pl, f, std::min(step, pl->total - f), nullptr, ck));
     uint64_t h[2];
     LIME_TRY(read_back(ctx, h, ck, 16));
-    release(ctx, ck);
     *sum = h[0];
     *xr = h[1];
     return LIME_OK;
@@ -1172,7 +1182,7 @@ int64_t plan_total(const PairsPlan *pl) { return pl->total; }
 int window_plan(lime_ctx *ctx, const lime_set *A, const lime_set *B, int64_t d,
                 PairsPlan **out) {
     if (d < 1) return intersect_plan(ctx, A, B, 0, -1, -1, out, A, 0);
-    lime_set *W = new lime_set();
+    std::unique_ptr<lime_set, DropWidened> W(new lime_set());
     W->ctx = ctx;
     W->n = A->n;
     W->row = A->row;  // borrowed: W's row i is A's row i
@@ -1184,13 +1194,8 @@ int window_plan(lime_ctx *ctx, const lime_set *A, const lime_set *B, int64_t d,
     W->min_width = A->min_width;
     W->max_width = A->max_width;
     W->has_zero_width = false;  // every W row is >= 2d wide or clipped to > 0
-    int rc = LIME_OK;
-    if ((rc = alloc(ctx, &W->gs, (size_t)std::max<int64_t>(A->n, 1))) ||
-        (rc = alloc(ctx, &W->ge, (size_t)std::max<int64_t>(A->n, 1)))) {
-        release(ctx, W->gs);
-        delete W;
-        return rc;
-    }
+    LIME_TRY(alloc(ctx, &W->gs, (size_t)std::max<int64_t>(A->n, 1)));
+    LIME_TRY(alloc(ctx, &W->ge, (size_t)std::max<int64_t>(A->n, 1)));
     if (A->n > 0) {
         hipLaunchKernelGGL(k_widen, dim3(blocks_for(A->n, 256)), dim3(256), 0, S(ctx), A->gs,
                            A->ge, A->n, d, (const uint32_t *)A->d_off, A->n_contigs, W->gs,
@@ -1198,31 +1203,12 @@ int window_plan(lime_ctx *ctx, const lime_set *A, const lime_set *B, int64_t d,
         LIME_HIP(hipGetLastError());
     }
     PairsPlan *pl = nullptr;
-    rc = intersect_plan(ctx, W, B, 0, -1, -1, &pl, A, d);
-    if (rc != LIME_OK) {
-        release(ctx, W->gs);
-        release(ctx, W->ge);
-        delete W;
-        return rc;
-    }
-    pl->W = W;
+    LIME_TRY(intersect_plan(ctx, W.get(), B, 0, -1, -1, &pl, A, d));
+    pl->W = std::move(W);
     *out = pl;
     return LIME_OK;
 }
 
-void intersect_free(PairsPlan *pl) {
-    lime_ctx *ctx = pl->ctx;
-    if (pl->W) {
-        release(ctx, pl->W->gs);
-        release(ctx, pl->W->ge);
-        delete pl->W;
-    }
-    release(ctx, pl->olo);
-    release(ctx, pl->ocnt);
-    release(ctx, pl->toff);
-    release(ctx, pl->win);
-    release(ctx, pl->tseg);
-    delete pl;
-}
+void intersect_free(PairsPlan *pl) { delete pl; }
 
 }  // namespace lime

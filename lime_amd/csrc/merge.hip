@@ -587,14 +587,12 @@ __global__ __launch_bounds__(MB) void k_prefix_max(const uint32_t *__restrict__ 
     }
 }
 
-int tile_prefix(lime_ctx *ctx, const uint32_t *ge, int64_t n, uint32_t **tpre_out) {
+int tile_prefix(lime_ctx *ctx, const uint32_t *ge, int64_t n, PoolPtr<uint32_t> &tpre) {
     const int64_t nt = (n + MTILE - 1) / MTILE;
-    uint32_t *tpre;
-    LIME_TRY(alloc(ctx, &tpre, (size_t)nt));
-    hipLaunchKernelGGL(k_tile_max, dim3((unsigned)nt), dim3(MB), 0, S(ctx), ge, n, tpre);
-    hipLaunchKernelGGL(k_scan_max, dim3(1), dim3(MB), 0, S(ctx), tpre, nt);
+    LIME_TRY(tpre.alloc(ctx, (size_t)nt));
+    hipLaunchKernelGGL(k_tile_max, dim3((unsigned)nt), dim3(MB), 0, S(ctx), ge, n, tpre.get());
+    hipLaunchKernelGGL(k_scan_max, dim3(1), dim3(MB), 0, S(ctx), tpre.get(), nt);
     LIME_HIP(hipGetLastError());
-    *tpre_out = tpre;
     return LIME_OK;
 }
 
@@ -602,13 +600,12 @@ int tile_prefix(lime_ctx *ctx, const uint32_t *ge, int64_t n, uint32_t **tpre_ou
 
 int prefix_max_u32(lime_ctx *ctx, const uint32_t *in, uint32_t *out, int64_t n) {
     if (n <= 0) return LIME_OK;
-    uint32_t *tpre;
-    LIME_TRY(tile_prefix(ctx, in, n, &tpre));
+    PoolPtr<uint32_t> tpre;
+    LIME_TRY(tile_prefix(ctx, in, n, tpre));
     const int64_t nt = (n + MTILE - 1) / MTILE;
     hipLaunchKernelGGL(k_prefix_max, dim3((unsigned)nt), dim3(MB), 0, S(ctx), in, n,
                        (const uint32_t *)tpre, out);
     LIME_HIP(hipGetLastError());
-    release(ctx, tpre);
     return LIME_OK;
 }
 
@@ -619,10 +616,10 @@ int build_prefix_max(lime_ctx *ctx, const lime_set *set) {
     if (set->ctx != ctx) return fail(LIME_ERR_ARG, "set belongs to another context");
     std::lock_guard<std::mutex> lock(set->ctx->mu);
     if (set->pmax) return LIME_OK;
-    uint32_t *pm;
-    LIME_TRY(alloc(set->ctx, &pm, (size_t)set->n));
+    PoolPtr<uint32_t> pm;
+    LIME_TRY(pm.alloc(set->ctx, (size_t)set->n));
     LIME_TRY(prefix_max_u32(set->ctx, set->ge, pm, set->n));
-    set->pmax = pm;
+    set->pmax = pm.take();
     return LIME_OK;
 }
 
@@ -643,15 +640,15 @@ static int merge_runs_impl(lime_ctx *ctx, const lime_set *set, lime_result *res,
     const int64_t nt = (n + (plain ? G2::TILE : STILE) - 1) / (plain ? G2::TILE : STILE);
     // status words of both chains + ticket + total + tie flag in one zeroed
     // block
-    uint64_t *st;
-    LIME_TRY(alloc(ctx, &st, (size_t)(2 * nt + 3)));
+    PoolPtr<uint64_t> st;
+    LIME_TRY(st.alloc(ctx, (size_t)(2 * nt + 3)));
     LIME_HIP(hipMemsetAsync(st, 0, sizeof(uint64_t) * (size_t)(2 * nt + 3), S(ctx)));
-    uint32_t *run_gs, *run_ge;
-    LIME_TRY(alloc(ctx, &run_gs, (size_t)n));
-    LIME_TRY(alloc(ctx, &run_ge, (size_t)n));
+    PoolPtr<uint32_t> run_gs, run_ge;
+    LIME_TRY(run_gs.alloc(ctx, (size_t)n));
+    LIME_TRY(run_ge.alloc(ctx, (size_t)n));
     if (want_run_ids) LIME_TRY(alloc(ctx, &res->run_of_sorted, (size_t)n));
-    int8_t *run_st = nullptr;  // stranded sets: the strand of every run
-    if (set->strand_in) LIME_TRY(alloc(ctx, &run_st, (size_t)n));
+    PoolPtr<int8_t> run_st;  // stranded sets: the strand of every run
+    if (set->strand_in) LIME_TRY(run_st.alloc(ctx, (size_t)n));
     MergeScanArgs a;
     a.gs = set->gs;
     a.ge = set->ge;
@@ -684,12 +681,12 @@ static int merge_runs_impl(lime_ctx *ctx, const lime_set *set, lime_result *res,
     } else {
         LIME_TRY(read_back(ctx, &nr, a.total, sizeof(nr)));
     }
-    release(ctx, st);
+    st.reset();
     if (nr * 2 > (uint64_t)n) {
         // most rows start a run: keep the capacity-n arrays
-        res->gs = run_gs;
-        res->ge = run_ge;
-        res->run_strand = run_st;
+        res->gs = run_gs.take();
+        res->ge = run_ge.take();
+        res->run_strand = run_st.take();
     } else {
         LIME_TRY(alloc(ctx, &res->gs, (size_t)nr));
         LIME_TRY(alloc(ctx, &res->ge, (size_t)nr));
@@ -697,13 +694,12 @@ static int merge_runs_impl(lime_ctx *ctx, const lime_set *set, lime_result *res,
                                 S(ctx)));
         LIME_HIP(hipMemcpyAsync(res->ge, run_ge, sizeof(uint32_t) * nr, hipMemcpyDeviceToDevice,
                                 S(ctx)));
-        release(ctx, run_gs);
-        release(ctx, run_ge);
+        run_gs.reset();
+        run_ge.reset();
         if (run_st) {
             LIME_TRY(alloc(ctx, &res->run_strand, (size_t)std::max<uint64_t>(nr, 1)));
             LIME_HIP(hipMemcpyAsync(res->run_strand, run_st, (size_t)nr, hipMemcpyDeviceToDevice,
                                     S(ctx)));
-            release(ctx, run_st);
         }
     }
     res->n = (int64_t)nr;
@@ -727,14 +723,10 @@ int merge_runs_with_pmax(lime_ctx *ctx, const lime_set *set, lime_result *res, i
     }
     std::lock_guard<std::mutex> lock(set->ctx->mu);
     if (set->pmax) return merge_runs_impl(ctx, set, res, true, nullptr, tie_big);
-    uint32_t *pm;
-    LIME_TRY(alloc(set->ctx, &pm, (size_t)set->n));
-    const int rc = merge_runs_impl(ctx, set, res, true, pm, tie_big);
-    if (rc != LIME_OK) {
-        release(set->ctx, pm);
-        return rc;
-    }
-    set->pmax = pm;
+    PoolPtr<uint32_t> pm;
+    LIME_TRY(pm.alloc(set->ctx, (size_t)set->n));
+    LIME_TRY(merge_runs_impl(ctx, set, res, true, pm, tie_big));
+    set->pmax = pm.take();
     return LIME_OK;
 }
 

@@ -337,19 +337,15 @@ int route_rows(lime_ctx *ctx, const lime_space *sp, int64_t n, const int32_t *d_
         if (splits[r + 1] < splits[r]) return fail(LIME_ERR_ARG, "splits must be non-decreasing");
     const uint32_t nblk = (uint32_t)std::max<int64_t>((n + RBLK - 1) / RBLK, 1);
     const int64_t mlen = (int64_t)nsh * nblk + 1;
-    uint32_t *mat = nullptr, *d_split = nullptr;
+    PoolPtr<uint32_t> mat, d_split;
     const uint32_t *d_off = nullptr, *d_len = nullptr;  // the context's cached space arrays
-    unsigned int *err = nullptr;
-    int64_t *tot = nullptr;
-    LIME_TRY(alloc(ctx, &mat, (size_t)mlen));
-    PoolGuard<uint32_t> g0{ctx, mat};
-    LIME_TRY(alloc(ctx, &d_split, (size_t)nsh + 1));
-    PoolGuard<uint32_t> g1{ctx, d_split};
+    PoolPtr<unsigned int> err;
+    PoolPtr<int64_t> tot;
+    LIME_TRY(mat.alloc(ctx, (size_t)mlen));
+    LIME_TRY(d_split.alloc(ctx, (size_t)nsh + 1));
     LIME_TRY(space_device(ctx, sp->off, &d_off, &d_len));
-    LIME_TRY(alloc(ctx, &err, 1));
-    PoolGuard<unsigned int> g4{ctx, err};
-    LIME_TRY(alloc(ctx, &tot, (size_t)nsh + 2));
-    PoolGuard<int64_t> g5{ctx, tot};
+    LIME_TRY(err.alloc(ctx, 1));
+    LIME_TRY(tot.alloc(ctx, (size_t)nsh + 2));
     LIME_HIP(hipMemcpyAsync(d_split, splits, 4 * ((size_t)nsh + 1), hipMemcpyHostToDevice, S(ctx)));
     LIME_HIP(hipMemsetAsync(err, 0, 4, S(ctx)));
     LIME_HIP(hipMemsetAsync(mat, 0, 4 * (size_t)mlen, S(ctx)));

@@ -164,14 +164,13 @@ int scan_exclusive(lime_ctx *ctx, const T *in, T *out, int64_t n, T *total_dev) 
         return LIME_OK;
     }
     const int64_t nb = (n + STILE - 1) / STILE;
-    T *part = nullptr;
-    LIME_TRY(alloc(ctx, &part, (size_t)nb));
+    PoolPtr<T> part;
+    LIME_TRY(part.alloc(ctx, (size_t)nb));
     hipLaunchKernelGGL(k_reduce<T>, dim3((unsigned)nb), dim3(SB), 0, S(ctx), in, part, n);
     hipLaunchKernelGGL(k_scan_parts<T>, dim3(1), dim3(SB), 0, S(ctx), part, nb, total_dev);
     hipLaunchKernelGGL(k_scan_blocks<T>, dim3((unsigned)nb), dim3(SB), 0, S(ctx), in, out,
                        (const T *)part, n);
     LIME_HIP(hipGetLastError());
-    release(ctx, part);
     return LIME_OK;
 }
 

@@ -1644,8 +1644,8 @@ void launch_prep_w16(lime_ctx *ctx, lime_set *set, const int32_t *d_contig,
 template <int DB1, int DB2>
 int bucket_passes(lime_ctx *ctx, lime_set *set, bool global, const int32_t *d_contig,
                   const uint32_t *d_start, const uint32_t *d_end, int64_t n, int L, bool w16,
-                  uint32_t *mat, int mat_bits, uint32_t ntiles, uint32_t *const (&a)[3],
-                  uint32_t *const (&o)[3], const uint32_t *pk = nullptr,
+                  uint32_t *mat, int mat_bits, uint32_t ntiles, const PoolPtr<uint32_t> (&a)[3],
+                  const PoolPtr<uint32_t> (&o)[3], const uint32_t *pk = nullptr,
                   const uint32_t *pw = nullptr, bool pack = false, uint32_t *dstart1 = nullptr,
                   uint32_t *part = nullptr) {
     if (pack && (!w16 || L > 16 || !dstart1 || !part))
@@ -1706,8 +1706,8 @@ int sort_set_impl(lime_ctx *ctx, lime_set *set, bool global, const int32_t *d_co
                   const uint32_t *d_start, const uint32_t *d_end, const uint32_t *d_len) {
     const int64_t n = set->n;
     const uint32_t ntiles = (uint32_t)((n + RTILE - 1) / RTILE);
-    uint32_t *k0 = nullptr, *e0 = nullptr, *r0 = nullptr, *mat = nullptr;
-    SetStats *part, *st;
+    PoolPtr<uint32_t> k0, e0, r0, mat;
+    PoolPtr<SetStats> part, st;
     // binned sets (bitset painting) keep no row ids: 8 B per row per pass
     const bool keep_rows = set->min_shift == 0;
     const bool stranded = set->strand_in != nullptr;
@@ -1740,17 +1740,17 @@ int sort_set_impl(lime_ctx *ctx, lime_set *set, bool global, const int32_t *d_co
     const int DB1 = TB / 2, DB2 = TB - DB1;
     // (the digit-count matrix serves both bucket passes: sized for the wider)
     const int mat_bits = bucket_cand ? std::max(DB1, DB2) : 8;
-    LIME_TRY(alloc(ctx, &mat, ((size_t)1 << mat_bits) * (ntiles ? ntiles : 1)));
-    LIME_TRY(alloc(ctx, &part, (size_t)(ntiles ? ntiles : 1)));
-    LIME_TRY(alloc(ctx, &st, 1));
+    LIME_TRY(mat.alloc(ctx, ((size_t)1 << mat_bits) * (ntiles ? ntiles : 1)));
+    LIME_TRY(part.alloc(ctx, (size_t)(ntiles ? ntiles : 1)));
+    LIME_TRY(st.alloc(ctx, 1));
     const int hshift = bucket_cand ? sbits - TB : set->min_shift;
     SetStats h = {0u, 0u, 0xffffffffu, 0u, 0u, 0u, {0, 0}};
     if (n > 0) {
         if (bucket_cand && !global && LIME_SORT_W16) {
             // validate + statistics + histogram, and (gs, u16 width) for the
             // first pass (unused if a width reaches 2^16)
-            LIME_TRY(alloc(ctx, &k0, (size_t)n));
-            LIME_TRY(alloc(ctx, &e0, (size_t)(n + 1) / 2));
+            LIME_TRY(k0.alloc(ctx, (size_t)n));
+            LIME_TRY(e0.alloc(ctx, (size_t)(n + 1) / 2));
             if (DB1 == 9)
                 launch_prep_w16<9>(ctx, set, d_contig, d_start, d_end, d_len, n, k0, e0, part, mat,
                                    ntiles, hshift);
@@ -1765,9 +1765,9 @@ int sort_set_impl(lime_ctx *ctx, lime_set *set, bool global, const int32_t *d_co
                 launch_prep_nowrite<8>(ctx, set, global, d_contig, d_start, d_end, d_len, n, part,
                                        mat, ntiles, hshift);
         } else {
-            LIME_TRY(alloc(ctx, &k0, (size_t)n));
-            LIME_TRY(alloc(ctx, &e0, (size_t)n));
-            if (keep_rows) LIME_TRY(alloc(ctx, &r0, (size_t)n));
+            LIME_TRY(k0.alloc(ctx, (size_t)n));
+            LIME_TRY(e0.alloc(ctx, (size_t)n));
+            if (keep_rows) LIME_TRY(r0.alloc(ctx, (size_t)n));
             if (global)
                 hipLaunchKernelGGL(k_prep<true>, dim3(ntiles), dim3(RB), 0, S(ctx), d_contig,
                                    d_start, d_end, (const uint32_t *)set->d_off, d_len,
@@ -1787,13 +1787,9 @@ int sort_set_impl(lime_ctx *ctx, lime_set *set, bool global, const int32_t *d_co
         LIME_HIP(hipGetLastError());
         LIME_TRY(read_back(ctx, &h, st, sizeof(h)));
     }
-    release(ctx, part);
-    release(ctx, st);
+    part.reset();
+    st.reset();
     if (h.err) {
-        release(ctx, k0);
-        release(ctx, e0);
-        release(ctx, r0);
-        release(ctx, mat);
         if (h.err & 1u) return fail(LIME_ERR_CONTIG, "interval contig id outside the space");
         if (h.err & 2u) return fail(LIME_ERR_RANGE, "interval end < start");
         return fail(LIME_ERR_RANGE, "interval end beyond its contig length");
@@ -1813,21 +1809,20 @@ int sort_set_impl(lime_ctx *ctx, lime_set *set, bool global, const int32_t *d_co
         const uint32_t nb = (h.max_gs >> L) + 1;
         const int shape = local_shape(TB, n / (int64_t)nb);
         if (need && n / (int64_t)nb <= LAVG_W) {
-            uint32_t *a[3], *o[3];
+            PoolPtr<uint32_t> a[3], o[3];
             for (int q = 0; q < 3; ++q) {
-                LIME_TRY(alloc(ctx, &a[q], (size_t)n));
-                LIME_TRY(alloc(ctx, &o[q], (size_t)n));
+                LIME_TRY(a[q].alloc(ctx, (size_t)n));
+                LIME_TRY(o[q].alloc(ctx, (size_t)n));
             }
             const bool w16 = LIME_SORT_W16 && h.max_width < 65536u;
             // the packed second pass: (gs mod 2^L, width) in one word, the
             // buckets placed from the histogram partials (no key search)
             const bool pack = LIME_SORT_PACK && w16 && L <= 16;
-            uint32_t *dstart1 = nullptr, *part = nullptr;
+            PoolPtr<uint32_t> dstart1, part;
             if (pack) {
-                LIME_TRY(alloc(ctx, &dstart1, (size_t)1 << DB1));
-                LIME_TRY(alloc(ctx, &part, (size_t)1 << TB));
+                LIME_TRY(dstart1.alloc(ctx, (size_t)1 << DB1));
+                LIME_TRY(part.alloc(ctx, (size_t)1 << TB));
             }
-            PoolGuard<uint32_t> gd{ctx, dstart1}, gpart{ctx, part};
             if (TB == 16)
                 LIME_TRY((bucket_passes<8, 8>(ctx, set, global, d_contig, d_start, d_end, n, L, w16,
                                               mat, mat_bits, ntiles, a, o, k0, e0, pack, dstart1,
@@ -1840,17 +1835,14 @@ int sort_set_impl(lime_ctx *ctx, lime_set *set, bool global, const int32_t *d_co
                 LIME_TRY((bucket_passes<9, 9>(ctx, set, global, d_contig, d_start, d_end, n, L, w16,
                                               mat, mat_bits, ntiles, a, o, k0, e0, pack, dstart1,
                                               part)));
-            release(ctx, k0);
-            release(ctx, e0);
+            k0.reset();
+            e0.reset();
             // every bucket sorted locally: (o) -> (a)
-            uint32_t *start, *over;
-            unsigned int *nover;
-            LIME_TRY(alloc(ctx, &start, (size_t)nb + 1));
-            PoolGuard<uint32_t> g0{ctx, start};
-            LIME_TRY(alloc(ctx, &over, (size_t)nb));
-            PoolGuard<uint32_t> g1{ctx, over};
-            LIME_TRY(alloc(ctx, &nover, 2));
-            PoolGuard<unsigned int> g2{ctx, nover};
+            PoolPtr<uint32_t> start, over;
+            PoolPtr<unsigned int> nover;
+            LIME_TRY(start.alloc(ctx, (size_t)nb + 1));
+            LIME_TRY(over.alloc(ctx, (size_t)nb));
+            LIME_TRY(nover.alloc(ctx, 2));
             LIME_HIP(hipMemsetAsync(nover, 0, 8, S(ctx)));
             if (pack)
                 hipLaunchKernelGGL(k_bucket_starts_part, dim3(blocks_for((int64_t)nb + 1, 256)),
@@ -1860,7 +1852,7 @@ int sort_set_impl(lime_ctx *ctx, lime_set *set, bool global, const int32_t *d_co
             else
                 hipLaunchKernelGGL(k_bucket_starts, dim3(blocks_for((int64_t)nb + 1, 256)),
                                    dim3(256), 0, S(ctx), (const uint32_t *)o[0], n, nb, L, start);
-            release(ctx, mat);
+            mat.reset();
             LocalArgs la;
             la.k0 = o[0], la.e0 = o[1], la.r0 = o[2];
             la.start = start;
@@ -1869,9 +1861,8 @@ int sort_set_impl(lime_ctx *ctx, lime_set *set, bool global, const int32_t *d_co
             la.k1 = a[0], la.e1 = a[1], la.r1 = a[2];
             la.nover = nover;
             la.over = over;
-            uint32_t *sink;
-            LIME_TRY(alloc(ctx, &sink, (size_t)LSINK));
-            PoolGuard<uint32_t> g3{ctx, sink};
+            PoolPtr<uint32_t> sink;
+            LIME_TRY(sink.alloc(ctx, (size_t)LSINK));
             la.sink = sink;
             int dev = 0, cus = 256;
             (void)hipGetDevice(&dev);
@@ -1898,10 +1889,9 @@ int sort_set_impl(lime_ctx *ctx, lime_set *set, bool global, const int32_t *d_co
                 LIME_LOCAL_LAUNCH(false);
 #undef LIME_LOCAL_LAUNCH
             LIME_HIP(hipGetLastError());
-            for (int q = 0; q < 3; ++q) release(ctx, o[q]);
-            set->gs = a[0];
-            set->ge = a[1];
-            set->row = a[2];
+            set->gs = a[0].take();
+            set->ge = a[1].take();
+            set->row = a[2].take();
             // the first pass read the caller's arrays after the statistics
             // read-back: on the context's own stream the call returns only once
             // they are consumed (a caller stream orders their reuse itself)
@@ -1909,21 +1899,19 @@ int sort_set_impl(lime_ctx *ctx, lime_set *set, bool global, const int32_t *d_co
             return LIME_OK;
         }
         // (in order, or dense buckets) the digit-pass layout from the caller's rows
-        release(ctx, k0);  // (the speculative (gs, u16 width) of the prep)
-        release(ctx, e0);
-        LIME_TRY(alloc(ctx, &k0, (size_t)n));
-        LIME_TRY(alloc(ctx, &e0, (size_t)n));
-        LIME_TRY(alloc(ctx, &r0, (size_t)n));
+        k0.reset();  // (the speculative (gs, u16 width) of the prep)
+        e0.reset();
+        LIME_TRY(k0.alloc(ctx, (size_t)n));
+        LIME_TRY(e0.alloc(ctx, (size_t)n));
+        LIME_TRY(r0.alloc(ctx, (size_t)n));
         if (global) {
             LIME_HIP(hipMemcpyAsync(k0, d_contig, 4 * (size_t)n, hipMemcpyDeviceToDevice, S(ctx)));
             LIME_HIP(hipMemcpyAsync(e0, d_start, 4 * (size_t)n, hipMemcpyDeviceToDevice, S(ctx)));
             LIME_HIP(hipMemcpyAsync(r0, d_end, 4 * (size_t)n, hipMemcpyDeviceToDevice, S(ctx)));
         } else {
             // gs / ge, and the digit-0 histogram the passes below start from
-            PoolGuard<SetStats> gp{ctx, part};
-            PoolGuard<SetStats> gq{ctx, st};
-            LIME_TRY(alloc(ctx, &part, (size_t)ntiles));
-            LIME_TRY(alloc(ctx, &st, 1));
+            LIME_TRY(part.alloc(ctx, (size_t)ntiles));
+            LIME_TRY(st.alloc(ctx, 1));
             if (set->n_contigs <= PCMAX)
                 hipLaunchKernelGGL((k_prep<false, true, true>), dim3(ntiles), dim3(RB), 0, S(ctx),
                                    d_contig, d_start, d_end, (const uint32_t *)set->d_off, d_len,
@@ -1933,14 +1921,16 @@ int sort_set_impl(lime_ctx *ctx, lime_set *set, bool global, const int32_t *d_co
                                    d_start, d_end, (const uint32_t *)set->d_off, d_len,
                                    set->n_contigs, n, k0, e0, nullptr, part, mat, ntiles, 0);
             LIME_HIP(hipGetLastError());
+            part.reset();
+            st.reset();
         }
     }
 
     if (need) {
-        uint32_t *k1, *e1, *r1 = nullptr;
-        LIME_TRY(alloc(ctx, &k1, (size_t)n));
-        LIME_TRY(alloc(ctx, &e1, (size_t)n));
-        if (keep_rows) LIME_TRY(alloc(ctx, &r1, (size_t)n));
+        PoolPtr<uint32_t> k1, e1, r1;
+        LIME_TRY(k1.alloc(ctx, (size_t)n));
+        LIME_TRY(e1.alloc(ctx, (size_t)n));
+        if (keep_rows) LIME_TRY(r1.alloc(ctx, (size_t)n));
         std::vector<std::pair<int, int>> passes;  // (mode, shift), least significant first
         if (row_ties) {
             // (gs, ge, row): row digits, then width digits, then gs
@@ -1981,19 +1971,15 @@ int sort_set_impl(lime_ctx *ctx, lime_set *set, bool global, const int32_t *d_co
             std::swap(e0, e1);
             std::swap(r0, r1);
         }
-        release(ctx, k1);
-        release(ctx, e1);
-        release(ctx, r1);
     } else if (keep_rows && !global && n > 0) {
         // already in order: the row ids are the positions
         hipLaunchKernelGGL(k_rows_iota, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(ctx),
                            r0, n);
         LIME_HIP(hipGetLastError());
     }
-    release(ctx, mat);
-    set->gs = k0;
-    set->ge = e0;
-    set->row = r0;
+    set->gs = k0.take();
+    set->ge = e0.take();
+    set->row = r0.take();
     return LIME_OK;
 }
 

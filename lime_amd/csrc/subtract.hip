@@ -26,13 +26,11 @@
 // One thread per left row, two passes (count, write); the write pass stages
 // a block's records in LDS and stores them lane-consecutively.
 #include <type_traits>
+#include <utility>
 
 #include "common.hpp"
 
 namespace lime {
-
-int owner_ranges(lime_ctx *ctx, const lime_set *O, const lime_set *P, int st, int64_t threshold,
-                 uint32_t *olo, uint32_t *ocnt);
 
 namespace {
 
@@ -1457,9 +1455,6 @@ __global__ __launch_bounds__(256) void k_tie_compact(const uint32_t *__restrict_
 
 }  // namespace
 
-int sort_set_global(lime_ctx *ctx, lime_set *set, const uint32_t *d_gs, const uint32_t *d_ge,
-                    const uint32_t *d_row, const uint32_t *d_len);
-
 // B's tie index, built once per set (under its context's lock) when some
 // same-start group has more than TIE_G rows; else tie_n = 0.  known: whether
 // one has (the merge scan tests it on the runs path), -1 unknown
@@ -1471,11 +1466,9 @@ static int build_tie_index(lime_ctx *ctx, const lime_set *B, int known) {
         B->tie_n = 0;
         return LIME_OK;
     }
-    uint32_t *flag, *pos, *tot;
-    unsigned int *big;
-    LIME_TRY(alloc(ctx, &tot, 2));
-    PoolGuard<uint32_t> g2{ctx, tot};
-    big = reinterpret_cast<unsigned int *>(tot + 1);
+    PoolPtr<uint32_t> flag, pos, tot;
+    LIME_TRY(tot.alloc(ctx, 2));
+    unsigned int *big = reinterpret_cast<unsigned int *>(tot + 1);
     LIME_HIP(hipMemsetAsync(tot, 0, 8, S(ctx)));
     // (most sets have no long same-start group: one read of gs decides)
     if (known < 0) {
@@ -1489,10 +1482,8 @@ static int build_tie_index(lime_ctx *ctx, const lime_set *B, int known) {
             return LIME_OK;
         }
     }
-    LIME_TRY(alloc(ctx, &flag, (size_t)n));
-    PoolGuard<uint32_t> g0{ctx, flag};
-    LIME_TRY(alloc(ctx, &pos, (size_t)n));
-    PoolGuard<uint32_t> g1{ctx, pos};
+    LIME_TRY(flag.alloc(ctx, (size_t)n));
+    LIME_TRY(pos.alloc(ctx, (size_t)n));
     hipLaunchKernelGGL(k_tie_flags, dim3(blocks_for(n, 256)), dim3(256), 0, S(ctx), B->gs, n, flag,
                        big);
     LIME_TRY(scan_exclusive_u32(ctx, flag, pos, n, tot));
@@ -1503,17 +1494,14 @@ static int build_tie_index(lime_ctx *ctx, const lime_set *B, int known) {
         return LIME_OK;
     }
     const int64_t T = h[0];
-    uint32_t *tg, *te, *tr;
-    LIME_TRY(alloc(ctx, &tg, (size_t)T));
-    PoolGuard<uint32_t> g3{ctx, tg};
-    LIME_TRY(alloc(ctx, &te, (size_t)T));
-    PoolGuard<uint32_t> g4{ctx, te};
-    LIME_TRY(alloc(ctx, &tr, (size_t)T));
-    PoolGuard<uint32_t> g5{ctx, tr};
+    PoolPtr<uint32_t> tg, te, tr;
+    LIME_TRY(tg.alloc(ctx, (size_t)T));
+    LIME_TRY(te.alloc(ctx, (size_t)T));
+    LIME_TRY(tr.alloc(ctx, (size_t)T));
     hipLaunchKernelGGL(k_tie_compact, dim3(blocks_for(n, 256)), dim3(256), 0, S(ctx), B->gs, B->ge,
                        B->row, n, (const uint32_t *)flag, (const uint32_t *)pos, tg, te, tr);
     LIME_HIP(hipGetLastError());
-    lime_set t;  // (gs, ge, row) order
+    lime_set t;  // (gs, ge, row) order; its sorted arrays move into B
     t.ctx = ctx;
     t.n = T;
     t.d_off = B->d_off;
@@ -1522,15 +1510,12 @@ static int build_tie_index(lime_ctx *ctx, const lime_set *B, int known) {
     t.len = B->len;
     t.row_ties = true;
     LIME_TRY(sort_set_global(ctx, &t, tg, te, tr, nullptr));
-    B->tie_gs = t.gs;
-    B->tie_ge = t.ge;
-    B->tie_row = t.row;
+    B->tie_gs = std::exchange(t.gs, nullptr);
+    B->tie_ge = std::exchange(t.ge, nullptr);
+    B->tie_row = std::exchange(t.row, nullptr);
     B->tie_n = T;
     return LIME_OK;
 }
-
-int merge_runs(lime_ctx *ctx, const lime_set *set, lime_result *res, bool want_run_ids);
-int merge_runs_with_pmax(lime_ctx *ctx, const lime_set *set, lime_result *res, int *tie_big);
 
 int subtract_run(lime_ctx *ctx, const lime_set *A, const lime_set *B, int64_t threshold, int mode,
                  lime_result *res) {
@@ -1546,48 +1531,39 @@ int subtract_run(lime_ctx *ctx, const lime_set *A, const lime_set *B, int64_t th
     // threshold <= 0: blocks are B's merge runs (k_subtract<_, true>); the
     // runs of a stranded set also break at strand changes, so those walk
     const bool runs = threshold <= 0 && B->n > 0 && B->strand_in == nullptr;
+    LazyScope lazy(B);  // (B's prefix max and tie index, when built below)
     // B's prefix max: with the runs, out of the same merge scan (below)
     if (!runs) LIME_TRY(build_prefix_max(ctx, B));
     // runs: the count (k_sub_count_runs) and write passes find each row's
     // inside-hit range in their staged windows, no owner_ranges pass
     const bool inl = runs;
-    uint32_t *olo = nullptr, *ocnt = nullptr;
-    uint64_t *cnt, *off;
+    PoolPtr<uint32_t> olo, ocnt;
+    PoolPtr<uint64_t> cnt, off;
     if (!inl) {
-        LIME_TRY(alloc(ctx, &olo, (size_t)na));
-        LIME_TRY(alloc(ctx, &ocnt, (size_t)na));
+        LIME_TRY(olo.alloc(ctx, (size_t)na));
+        LIME_TRY(ocnt.alloc(ctx, (size_t)na));
     }
-    PoolGuard<uint32_t> go1{ctx, olo}, go2{ctx, ocnt};
-    LIME_TRY(alloc(ctx, &cnt, (size_t)na + 1));
-    PoolGuard<uint64_t> gc{ctx, cnt};
-    LIME_TRY(alloc(ctx, &off, (size_t)na + 1));
-    PoolGuard<uint64_t> go{ctx, off};
-    unsigned int *err;
-    LIME_TRY(alloc(ctx, &err, 1));
-    PoolGuard<unsigned int> ge{ctx, err};
+    LIME_TRY(cnt.alloc(ctx, (size_t)na + 1));
+    LIME_TRY(off.alloc(ctx, (size_t)na + 1));
+    PoolPtr<unsigned int> err;
+    LIME_TRY(err.alloc(ctx, 1));
     LIME_HIP(hipMemsetAsync(err, 0, 4, S(ctx)));
     if (!inl) LIME_TRY(owner_ranges(ctx, A, B, 0, threshold, olo, ocnt));
     const int64_t nblk = (na + SUB_B - 1) / SUB_B;
     // runs: B's merge runs with their run ids and B's prefix max (one scan)
     lime_result mb;
     mb.ctx = ctx;
-    PoolGuard<uint32_t> g1{ctx, mb.run_of_sorted};
-    PoolGuard<uint32_t> g2{ctx, mb.gs};
-    PoolGuard<uint32_t> g3{ctx, mb.ge};
     // LS (k_sub_fused<true>): B without zero-width rows and every fused
     // tile's window within FWIN (one read-back) -- no merge scan of B
-    uint32_t *wstart = nullptr, *wend = nullptr;
-    PoolGuard<uint32_t> gw{ctx, wstart};
-    PoolGuard<uint32_t> gwe{ctx, wend};
+    PoolPtr<uint32_t> wstart, wend;
     bool ls = false;
     // (LIME_SUB_NO_LS set: the merge-scan paths, as tests force them)
     if (runs && !B->has_zero_width && !getenv("LIME_SUB_NO_LS")) {
         const int64_t nt = blocks_for(na, FROWS);
-        unsigned int *wm;
-        LIME_TRY(alloc(ctx, &wm, 1));
-        PoolGuard<unsigned int> gm{ctx, wm};
-        LIME_TRY(alloc(ctx, &wstart, (size_t)nt));
-        LIME_TRY(alloc(ctx, &wend, (size_t)nt));
+        PoolPtr<unsigned int> wm;
+        LIME_TRY(wm.alloc(ctx, 1));
+        LIME_TRY(wstart.alloc(ctx, (size_t)nt));
+        LIME_TRY(wend.alloc(ctx, (size_t)nt));
         LIME_HIP(hipMemsetAsync(wm, 0, 4, S(ctx)));
         hipLaunchKernelGGL(k_sub_window, dim3(blocks_for(nt, 256)), dim3(256), 0, S(ctx), A->gs,
                            na, B->gs, B->n, B->max_width, nt, FW, wstart, A->max_width, wend, wm);
@@ -1596,9 +1572,8 @@ int subtract_run(lime_ctx *ctx, const lime_set *A, const lime_set *B, int64_t th
         LIME_TRY(read_back(ctx, &h_wm, wm, sizeof(h_wm)));
         ls = h_wm <= (unsigned)FWIN;
         if (!ls) {
-            release(ctx, wstart);
-            release(ctx, wend);
-            wstart = wend = nullptr;
+            wstart.reset();
+            wend.reset();
         }
     }
     // (the same scan tells whether B has a same-start group past TIE_G)
@@ -1619,8 +1594,8 @@ int subtract_run(lime_ctx *ctx, const lime_set *A, const lime_set *B, int64_t th
     const int stride = fused ? FW : inl ? CNT_WAVES : 1;
     const int64_t nws = (nblk + stride - 1) / stride;
     if (!ls) {
-        LIME_TRY(alloc(ctx, &wstart, (size_t)nws));
-        if (fused) LIME_TRY(alloc(ctx, &wend, (size_t)nws));
+        LIME_TRY(wstart.alloc(ctx, (size_t)nws));
+        if (fused) LIME_TRY(wend.alloc(ctx, (size_t)nws));
         if (B->n > 0)
             hipLaunchKernelGGL(k_sub_window, dim3(blocks_for(nws, 256)), dim3(256), 0, S(ctx),
                                A->gs, na, B->gs, B->n, B->max_width, nws, stride, wstart,
@@ -1628,12 +1603,10 @@ int subtract_run(lime_ctx *ctx, const lime_set *A, const lime_set *B, int64_t th
         else
             LIME_HIP(hipMemsetAsync(wstart, 0, 4 * (size_t)nws, S(ctx)));
     }
-    uint32_t *bwlo = nullptr;  // runs: per-block window starts (count -> write pass)
-    if (inl) LIME_TRY(alloc(ctx, &bwlo, (size_t)nblk));
-    PoolGuard<uint32_t> gb{ctx, bwlo};
-    uint8_t *rcnt = nullptr;  // runs: per-row record counts (count -> write pass)
-    if (inl) LIME_TRY(alloc(ctx, &rcnt, (size_t)na));
-    PoolGuard<uint8_t> gr{ctx, rcnt};
+    PoolPtr<uint32_t> bwlo;  // runs: per-block window starts (count -> write pass)
+    if (inl) LIME_TRY(bwlo.alloc(ctx, (size_t)nblk));
+    PoolPtr<uint8_t> rcnt;  // runs: per-row record counts (count -> write pass)
+    if (inl) LIME_TRY(rcnt.alloc(ctx, (size_t)na));
     SubArgs sa;
     sa.wstart = wstart;
     sa.wend = wend;
@@ -1686,9 +1659,8 @@ int subtract_run(lime_ctx *ctx, const lime_set *A, const lime_set *B, int64_t th
     }
     if (fused) {  // one pass: counts, places (look-back) and records
         const int64_t ntiles = blocks_for(na, FROWS);
-        uint64_t *st;
-        LIME_TRY(alloc(ctx, &st, (size_t)ntiles + 3));  // + ticket, total, error flags
-        PoolGuard<uint64_t> gs_{ctx, st};
+        PoolPtr<uint64_t> st;
+        LIME_TRY(st.alloc(ctx, (size_t)ntiles + 3));  // + ticket, total, error flags
         FusedArgs fa;
         fa.st = st;
         fa.ticket = reinterpret_cast<unsigned int *>(st + ntiles);
@@ -1700,25 +1672,19 @@ int subtract_run(lime_ctx *ctx, const lime_set *A, const lime_set *B, int64_t th
         // again at the exact total
         uint64_t cap = (uint64_t)na + 4096, total = 0;
         unsigned int fe = 0;
-        auto drop = [&]() {  // (nulled: a failed call's result is deleted)
-            for (uint32_t **p : {&res->gs, &res->ge, &res->a_row, &res->b_row}) {
-                release(ctx, *p);
-                *p = nullptr;
-            }
-        };
+        PoolPtr<uint32_t> o[4];  // gs, ge, a_row, b_row: the result's on success
         // test hook: LIME_TEST_SUB_SKEW=1 reports one record more on the second
         // pass than its capacity, so the disagreement guard below is exercised
         const char *skew_env = getenv("LIME_TEST_SUB_SKEW");
         const uint64_t skew = (skew_env && skew_env[0] == '1') ? 1 : 0;
         for (int attempt = 0, tie_runs = 0; attempt < 2; ++attempt) {
-            LIME_TRY(alloc(ctx, &res->gs, (size_t)cap));
-            LIME_TRY(alloc(ctx, &res->ge, (size_t)cap));
-            LIME_TRY(alloc(ctx, &res->a_row, (size_t)cap));
-            LIME_TRY(alloc(ctx, &res->b_row, (size_t)cap));
-            sa.ogs = res->gs;
-            sa.oge = res->ge;
-            sa.oar = res->a_row;
-            sa.obr = res->b_row;
+            // (a repeated pass: the arrays of the one before go back first)
+            for (auto &p : o) p.reset();
+            for (auto &p : o) LIME_TRY(p.alloc(ctx, (size_t)cap));
+            sa.ogs = o[0];
+            sa.oge = o[1];
+            sa.oar = o[2];
+            sa.obr = o[3];
             fa.cap = cap;
             LIME_HIP(hipMemsetAsync(st, 0, 8 * ((size_t)ntiles + 3), S(ctx)));
             if (ls)
@@ -1742,13 +1708,11 @@ int subtract_run(lime_ctx *ctx, const lime_set *A, const lime_set *B, int64_t th
                     if (tie_runs++) return fail(LIME_ERR_DEVICE, "subtract: tie index missing");
                     LIME_TRY(build_tie_index(ctx, B, 1));
                     tie_args();
-                    drop();
                     --attempt;
                     continue;
                 }
             }
             if (total <= cap) break;
-            drop();
             // the second attempt ran at the first one's exact total: a larger
             // total means the passes disagree (the arrays held only cap)
             if (attempt == 1)
@@ -1756,7 +1720,12 @@ int subtract_run(lime_ctx *ctx, const lime_set *A, const lime_set *B, int64_t th
             cap = total;
         }
         if (fe) return fail(LIME_ERR_DEVICE, "subtract: the writing fold differs from the count");
+        res->gs = o[0].take();
+        res->ge = o[1].take();
+        res->a_row = o[2].take();
+        res->b_row = o[3].take();
         res->n = (int64_t)total;
+        lazy.keep();
         return LIME_OK;
     }
     // runs write pass with records rare (under one per 16 blocks): the
@@ -1799,6 +1768,7 @@ int subtract_run(lime_ctx *ctx, const lime_set *A, const lime_set *B, int64_t th
         if (e) return fail(LIME_ERR_DEVICE, "subtract: write pass recount differs from the count pass");
     }
     res->n = (int64_t)total;
+    lazy.keep();
     return LIME_OK;
 }
 

@@ -97,9 +97,9 @@ int synth(lime_ctx *ctx, const lime_space *sp, int kind, int64_t first, int64_t 
         base[c + 1] = base[c] + len[c];
     }
     if (base[sp->n] == 0) return fail(LIME_ERR_ARG, "empty genome");
-    uint64_t *d_base, *d_len;
-    LIME_TRY(alloc(ctx, &d_base, base.size()));
-    LIME_TRY(alloc(ctx, &d_len, len.size()));
+    PoolPtr<uint64_t> d_base, d_len;
+    LIME_TRY(d_base.alloc(ctx, base.size()));
+    LIME_TRY(d_len.alloc(ctx, len.size()));
     LIME_HIP(hipMemcpyAsync(d_base, base.data(), base.size() * 8, hipMemcpyHostToDevice, S(ctx)));
     LIME_HIP(hipMemcpyAsync(d_len, len.data(), len.size() * 8, hipMemcpyHostToDevice, S(ctx)));
     SynthArgs a;
@@ -126,8 +126,6 @@ int synth(lime_ctx *ctx, const lime_space *sp, int kind, int64_t first, int64_t 
     LIME_HIP(hipGetLastError());
     // keep the tables alive until the kernel has consumed them
     LIME_HIP(hipStreamSynchronize(S(ctx)));
-    release(ctx, d_base);
-    release(ctx, d_len);
     return LIME_OK;
 }
 
