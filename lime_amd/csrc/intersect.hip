@@ -760,16 +760,27 @@ __global__ __launch_bounds__(FB, 2 * LIME_FILL_WGS) void k_fill(FillArgs fa, int
         const int64_t le = min(oend - tbase, (int64_t)ttot);
         // equal shares: `rounds` granules per wave of ~GR records each, so no
         // wave idles at the commit's closing barrier
-        const int64_t rounds = max((int64_t)1, (le - lb + FW * gran - 1) / (FW * gran));
-        const int64_t gsz = (((le - lb + FW * rounds - 1) / (FW * rounds)) + 63) & ~(int64_t)63;
+        // A tile starts at any record of the window, so a wave's 64-record
+        // store would straddle 1-KiB segments of `out` (9 lines touched for 8
+        // written, a partial line at either end) through the whole tile.  The
+        // granules are laid from the segment boundary at or below the slice's
+        // first record instead (lb0 <= lb): every store of waves 1 .. 7 is one
+        // whole segment; in wave 0's first granule the lanes below lb run one
+        // round ahead of the others (its stores split over two segments).
+        const int64_t lb0 = TPF == 1 ? lb - ((tbase + lb - fa.first) & 63) : lb;
+        const int64_t rounds = max((int64_t)1, (le - lb0 + FW * gran - 1) / (FW * gran));
+        const int64_t gsz = (((le - lb0 + FW * rounds - 1) / (FW * rounds)) + 63) & ~(int64_t)63;
         int qw = 0;  // wave-uniform: owner of the wave's previous granule start
-        for (int64_t gb = lb + (int64_t)w * gsz; gb < le; gb += (int64_t)FW * gsz) {
+        for (int64_t gb = lb0 + (int64_t)w * gsz; gb < le; gb += (int64_t)FW * gsz) {
             const int64_t gend = min(le, gb + gsz);
+            // (gb < lb: wave 0's first granule only; its lanes below lb start one round on)
+            const int64_t gs = TPF == 1 ? max(gb, lb) : gb;
             int64_t o = gb + lane;
-            // owner of the wave's first output (largest q with off_q <= gb),
+            if (TPF == 1 && o < lb) o += 64;
+            // owner of the wave's first output (largest q with off_q <= gs),
             // by a 65-ary wave search over the LDS offsets (2-3 steps); each
             // lane then walks to its own owner
-            qw = wave_owner_of(s_lo_off, qw, nown, (uint32_t)gb);
+            qw = wave_owner_of(s_lo_off, qw, nown, (uint32_t)gs);
             int q = qw;
             if (TPF > 1) {
                 uint32_t *wslot = s_wslot[TPF > 1 ? w : 0];
