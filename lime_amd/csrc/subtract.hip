@@ -849,8 +849,9 @@ __global__ __launch_bounds__(CNT_WAVES * 64) void k_sub_count_runs(SubArgs sa, i
 #define LIME_SUB_FWIN (384 * LIME_SUB_FW)
 #endif
 constexpr int FCAP = LIME_SUB_FCAP;
-// 1024 left rows per tile, the count pass's window (2048-row tiles with a
-// 3072-row window: the sparse 1e9-row subtract's pass 9.6 -> 10.2 ms)
+// FW waves of SUB_B left rows per tile: 2048 rows at FW = 8 (half the ticket
+// atomics of 1024-row tiles, which bounded the pass), a window of up to 3072
+// rows of B and 896 staged records
 constexpr int FW = LIME_SUB_FW, FROWS = FW * SUB_B, FWIN = LIME_SUB_FWIN;
 struct FusedArgs {
     uint64_t *st;          // per-tile status words (zeroed)
