@@ -284,6 +284,25 @@ int lime_subtract(lime_ctx *ctx, const lime_set *a, const lime_set *b, int64_t t
                   int mode, lime_result **out, int64_t *n_regions);
 int lime_complement(lime_ctx *ctx, const lime_space *genome_space, const lime_set *a,
                     lime_result **out, int64_t *n_regions);
+/* Depth of coverage (the reference's cli/Coverage.scala names the command;
+ * the result is what bedtools genomecov -bg reports): depth(p) = the rows
+ * with start <= p < end, and the result is every maximal interval inside one
+ * contig on which the depth is constant and >= 1, with that depth, contigs in
+ * String order and ascending inside a contig.  Zero-width rows add nothing,
+ * book-ended rows [0,5) [5,9) give ONE run of depth 1 (lime_merge gives two),
+ * strand is ignored (plain and stranded sets alike).  Zero-depth regions are
+ * lime_complement's. */
+int lime_coverage(lime_ctx *ctx, const lime_set *a, lime_result **out, int64_t *n_runs);
+/* coverage results only (LIME_ERR_ARG otherwise): depths of runs [first,
+ * first + count) to a host array; the device array (as many as the result has
+ * runs, owned by the result); and one device reduction over the runs:
+ * covered_bases = sum of widths, depth_bases = sum of width x depth (equal to
+ * the sum of the input rows' widths: the check at scale), max_depth.  Any of
+ * the three outputs may be NULL. */
+int lime_result_depths(const lime_result *res, int64_t first, int64_t count, uint32_t *depth);
+int lime_result_depth_device(const lime_result *res, const uint32_t **depth);
+int lime_result_depth_stats(const lime_result *res, uint64_t *covered_bases,
+                            uint64_t *depth_bases, uint32_t *max_depth);
 /* Gaps of sorted, disjoint runs already in HBM (global coordinates, e.g. a
  * coordinate shard's merged runs after the cross-shard carry) over the genome,
  * keeping only the gaps whose START lies in [lo, hi) -- a shard's share of
@@ -298,7 +317,8 @@ int lime_complement_runs(lime_ctx *ctx, const lime_space *genome, int64_t n,
                          lime_result **out, int64_t *n_regions);
 int64_t lime_result_size(const lime_result *res);
 /* Host copy of a result: regions in contig-local coordinates plus the
- * left/right input rows (-1 where the reference has None / no payload). */
+ * left/right input rows (-1 where the reference has None / no payload, and
+ * for every run of a coverage result). */
 int lime_result_fill_host(const lime_result *res, int32_t *contig, int64_t *start, int64_t *end,
                           int64_t *a_row, int64_t *b_row);
 /* merge only: run index of every input row (the Iterable[T] grouping). */
@@ -334,7 +354,8 @@ int lime_result_checksum(const lime_result *res, uint64_t *reg_sum, uint64_t *re
  * "chrom<TAB>start<TAB>end\n" lines in contig-local coordinates, into a
  * caller-owned HOST buffer.  names[c] = name of contig c of the object's
  * space (String order).  Two-call protocol: with cap < *len (e.g. out =
- * NULL, cap = 0) only the byte count *len is returned. */
+ * NULL, cap = 0) only the byte count *len is returned.  A coverage result
+ * writes "chrom<TAB>start<TAB>end<TAB>depth\n" (a bedGraph). */
 int lime_set_format_bed(const lime_set *set, const char *const *names, char *out, int64_t cap,
                         int64_t *len);
 int lime_result_format_bed(const lime_result *res, const char *const *names, char *out,

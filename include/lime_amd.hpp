@@ -10,6 +10,9 @@
 //       -> vector<pair<ReferenceRegion, pair<T, optional<U>>>> Subtract.scala:78-116
 //   DistributedComplement<T>(rdd, partitionMap, referenceNameBounds, threshold = 0).compute()
 //       -> vector<pair<ReferenceRegion, vector<T>>>           Complement.scala:131-134
+//   DistributedCoverage<T>(rdd, partitionMap).compute()
+//       -> vector<pair<ReferenceRegion, uint32_t>>            (depth runs; no lime-core
+//                                                              class, cli/Coverage.scala)
 //
 // An "RDD" is a host vector of (ReferenceRegion, value).  `partitionMap` is
 // accepted for signature parity and ignored: results equal the reference's
@@ -687,6 +690,51 @@ class DistributedComplement {
     PartitionMap pm_;
     std::map<std::string, ReferenceRegion> bounds_;
     int64_t threshold_;
+    Engine &eng_;
+};
+
+// Depth of coverage: (region, depth) for every maximal interval of one contig
+// on which the number of rows covering a base is constant and >= 1 (bedtools
+// genomecov -bg), contigs in RegionOrdering.  Not a lime-core class: the
+// reference has only the CLI stub cli/Coverage.scala; the name follows the
+// Distributed* family.  Strand is ignored, the regions are unstranded.
+template <class T>
+class DistributedCoverage {
+   public:
+    DistributedCoverage(RDD<T> rdd, PartitionMap partitionMap = {},
+                        Engine &eng = Engine::thread_default())
+        : rdd_(std::move(rdd)), pm_(std::move(partitionMap)), eng_(eng) {}
+
+    std::vector<std::pair<ReferenceRegion, uint32_t>> compute() {
+        auto gn = detail::space_of<T>({&rdd_});
+        auto parts = gn->split(rdd_, detail::all_rows(rdd_.size()));
+        std::vector<std::pair<ReferenceRegion, uint32_t>> out;
+        // contig-local: one space after the other
+        for (size_t q = 0; q < gn->spaces.size(); ++q) {
+            const auto &rows = parts[q];
+            if (rows.empty()) continue;
+            const auto &sp = *gn->spaces[q];
+            detail::SetHandle A;
+            detail::upload(eng_.ctx(), sp, rdd_, rows, A);
+            lime_result *res = nullptr;
+            int64_t cnt = 0;
+            check(lime_coverage(eng_.ctx(), A.h, &res, &cnt));
+            std::vector<int32_t> c((size_t)cnt);
+            std::vector<int64_t> s((size_t)cnt), e((size_t)cnt);
+            std::vector<uint32_t> d((size_t)cnt);
+            int rc = lime_result_fill_host(res, c.data(), s.data(), e.data(), nullptr, nullptr);
+            if (rc == LIME_OK) rc = lime_result_depths(res, 0, cnt, d.data());
+            lime_result_destroy(res);
+            check(rc);
+            for (int64_t k = 0; k < cnt; ++k)
+                out.push_back({ReferenceRegion(sp.names[c[k]], s[k], e[k]), d[k]});
+        }
+        return out;
+    }
+
+   private:
+    RDD<T> rdd_;
+    PartitionMap pm_;
     Engine &eng_;
 };
 

@@ -100,6 +100,10 @@ SIGNATURES = {
     "lime_merge": (C.c_int, [vp, vp, pp, P(i64)]),
     "lime_subtract": (C.c_int, [vp, vp, vp, i64, C.c_int, pp, P(i64)]),
     "lime_complement": (C.c_int, [vp, vp, vp, pp, P(i64)]),
+    "lime_coverage": (C.c_int, [vp, vp, pp, P(i64)]),
+    "lime_result_depths": (C.c_int, [vp, i64, i64, P(u32)]),
+    "lime_result_depth_device": (C.c_int, [vp, pp]),
+    "lime_result_depth_stats": (C.c_int, [vp, P(u64), P(u64), P(u32)]),
     "lime_complement_runs": (C.c_int, [vp, vp, i64, vp, vp, i64, i64, pp, P(i64)]),
     "lime_result_size": (i64, [vp]),
     "lime_result_fill_host": (C.c_int, [vp, P(i32), P(i64), P(i64), P(i64), P(i64)]),

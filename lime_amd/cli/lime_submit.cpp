@@ -15,6 +15,9 @@
 //                               DistributedWindow default distance 1000)
 //   closest   A.bed B.bed       cli/Closest.scala:45-58 (keys stranded,
 //                               SingleClosest)
+//   coverage  A.bed             cli/Coverage.scala (a stub in the reference, not
+//                               registered by LimeMain): the depth runs as
+//                               bedGraph lines chrom, start, end, depth
 //
 // Everything before "--" is accepted and ignored (there is no Spark).
 // Output is one region per line, tab-separated (chrom, start, end), followed
@@ -44,6 +47,7 @@ const Cmd kCommands[] = {
     {"window", "Compute nearby regions between two inputs"},
     {"cluster", "Cluster (but don't merge) overlapping/nearby intervals"},
     {"closest", "Find the closest region in the second input for each region of the first"},
+    {"coverage", "Compute the coverage over defined intervals"},
 };
 
 void usage() {
@@ -156,6 +160,13 @@ int run(const std::vector<std::string> &args) {
         for (auto &o : out) {
             print_region(o.first);
             printf("\t%zu\n", o.second.size());
+        }
+    } else if (cmd == "coverage") {
+        need(1);
+        auto out = DistributedCoverage<std::string>(load_bed(args[1], false)).compute();
+        for (auto &o : out) {
+            print_region(o.first);
+            printf("\t%u\n", o.second);
         }
     } else if (cmd == "complement") {
         need(2);

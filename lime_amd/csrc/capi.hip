@@ -220,6 +220,7 @@ lime_result::~lime_result() {
     lime::release(ctx, b_row);
     lime::release(ctx, run_of_sorted);
     lime::release(ctx, run_strand);
+    lime::release(ctx, depth);
 }
 
 void lime_bitset::drop_bins() {
@@ -1074,6 +1075,47 @@ int lime_subtract(lime_ctx *ctx, const lime_set *a, const lime_set *b, int64_t t
     return LIME_OK;
 }
 
+int lime_coverage(lime_ctx *ctx, const lime_set *a, lime_result **out, int64_t *n_runs) {
+    if (!ctx || !a || !out) return fail(LIME_ERR_ARG, "bad coverage arguments");
+    LIME_TRY(same_ctx(ctx, a));
+    if (a->min_shift) return fail(LIME_ERR_ARG, "coverage needs a fully sorted set");
+    hipSetDevice(ctx->device);
+    std::unique_ptr<lime_result> r = new_result(ctx, a);
+    LIME_TRY(coverage_run(ctx, a, r.get()));
+    if (n_runs) *n_runs = r->n;
+    *out = r.release();
+    return LIME_OK;
+}
+
+int lime_result_depths(const lime_result *r, int64_t first, int64_t count, uint32_t *depth) {
+    if (!r) return fail(LIME_ERR_ARG, "result is null");
+    if (!r->depth) return fail(LIME_ERR_ARG, "not a coverage result");
+    if (first < 0 || count < 0 || first + count > r->n || (count > 0 && !depth))
+        return fail(LIME_ERR_ARG, "range outside the result");
+    lime_ctx *ctx = r->ctx;
+    hipSetDevice(ctx->device);
+    if (count == 0) return LIME_OK;
+    LIME_HIP(hipMemcpyAsync(depth, r->depth + first, 4 * (size_t)count, hipMemcpyDeviceToHost,
+                            S(ctx)));
+    LIME_HIP(hipStreamSynchronize(S(ctx)));
+    return LIME_OK;
+}
+
+int lime_result_depth_device(const lime_result *r, const uint32_t **depth) {
+    if (!r || !depth) return fail(LIME_ERR_ARG, "bad arguments");
+    if (!r->depth) return fail(LIME_ERR_ARG, "not a coverage result");
+    *depth = r->depth;
+    return LIME_OK;
+}
+
+int lime_result_depth_stats(const lime_result *r, uint64_t *covered_bases, uint64_t *depth_bases,
+                            uint32_t *max_depth) {
+    if (!r) return fail(LIME_ERR_ARG, "result is null");
+    if (!r->depth) return fail(LIME_ERR_ARG, "not a coverage result");
+    hipSetDevice(r->ctx->device);
+    return depth_stats(r->ctx, r, covered_bases, depth_bases, max_depth);
+}
+
 int lime_complement(lime_ctx *ctx, const lime_space *genome, const lime_set *a, lime_result **out,
                     int64_t *n) {
     if (!ctx || !genome || !a || !out) return fail(LIME_ERR_ARG, "bad complement arguments");
@@ -1223,7 +1265,8 @@ int lime_result_format_bed(const lime_result *r, const char *const *names, char 
     std::vector<std::string> nm;
     LIME_TRY(names_of(names, r->n_contigs, nm));
     hipSetDevice(r->ctx->device);
-    return format_bed(r->ctx, r->off, nm, r->n, r->gs, r->ge, nullptr, out, cap, len);
+    // (a coverage result: its depths as the fourth column, a bedGraph)
+    return format_bed(r->ctx, r->off, nm, r->n, r->gs, r->ge, r->depth, out, cap, len);
 }
 
 int lime_result_device_arrays(const lime_result *r, const uint32_t **gs, const uint32_t **ge) {

@@ -162,6 +162,7 @@ struct lime_result {
     uint32_t *b_row = nullptr;  // may be null (0xffffffff = None)
     uint32_t *run_of_sorted = nullptr;  // merge only (per sorted input)
     int8_t *run_strand = nullptr;       // merge of a stranded set: strand per run
+    uint32_t *depth = nullptr;          // coverage only: depth of every run
     const lime_set *src = nullptr;      // merge only
     uint32_t *d_off = nullptr;          // contig offsets used to localise
     int32_t n_contigs = 0;
@@ -329,6 +330,11 @@ int merge_runs(lime_ctx *ctx, const lime_set *set, lime_result *res, bool want_r
 int merge_runs_with_pmax(lime_ctx *ctx, const lime_set *set, lime_result *res, int *tie_big);
 int subtract_run(lime_ctx *ctx, const lime_set *A, const lime_set *B, int64_t threshold, int mode,
                  lime_result *res);
+// depth-of-coverage runs of a sorted set (coverage.hip); res owns gs / ge / depth
+int coverage_run(lime_ctx *ctx, const lime_set *set, lime_result *res);
+// sum of widths, sum of width x depth and maximum depth of a coverage result
+int depth_stats(lime_ctx *ctx, const lime_result *res, uint64_t *covered, uint64_t *depth_bases,
+                uint32_t *max_depth);
 int complement_run(lime_ctx *ctx, const lime_result *runs, const uint32_t *d_off,
                    const uint32_t *d_len, int32_t nc, lime_result *res, uint32_t wlo = 0,
                    uint32_t whi = 0xffffffffu);

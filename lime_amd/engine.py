@@ -200,7 +200,8 @@ class Result:
         return out
 
     def to_bed(self):
-        """the result's regions as BED3 text, formatted on the device"""
+        """the result's regions as BED3 text, formatted on the device (a
+        coverage result: a bedGraph, the depth as the fourth column)"""
         return _format_bed(_lib().lime_result_format_bed, self._h, self.space)
 
     def checksum(self):
@@ -236,6 +237,27 @@ class Result:
         check(_lib().lime_result_run_strands(self._h, int(first), int(count),
                                              _ptr(out, C.c_int8)))
         return out[:count]
+
+    def depths(self, first=0, count=None):
+        """coverage results: depths of runs [first, first + count) (u32)"""
+        count = self.n - first if count is None else int(count)
+        out = np.zeros(max(count, 1), dtype=np.uint32)
+        check(_lib().lime_result_depths(self._h, int(first), count, _ptr(out, u32)))
+        return out[:count]
+
+    def depth_device(self):
+        """coverage results: device pointer of the runs' depths (u32)"""
+        d = vp()
+        check(_lib().lime_result_depth_device(self._h, C.byref(d)))
+        return d.value
+
+    def depth_stats(self):
+        """coverage results: (covered bases, sum of width x depth, max depth)
+        from one device reduction; the second equals the sum of the input
+        rows' widths"""
+        cov, db, mx = u64(), u64(), u32()
+        check(_lib().lime_result_depth_stats(self._h, C.byref(cov), C.byref(db), C.byref(mx)))
+        return cov.value, db.value, mx.value
 
     def copy_range(self, first, count):
         """host copy of regions [first, first+count) in GLOBAL coordinates"""
@@ -487,6 +509,13 @@ class Context:
         h, n = vp(), i64()
         check(_lib().lime_merge(self._h, a._h, C.byref(h), C.byref(n)))
         return Result(self, h, a.space, keep=(a,))
+
+    def coverage(self, a):
+        """depth of coverage: the maximal runs of constant depth >= 1 with
+        their depths (Result.depths / depth_stats; to_bed gives a bedGraph)"""
+        h, n = vp(), i64()
+        check(_lib().lime_coverage(self._h, a._h, C.byref(h), C.byref(n)))
+        return Result(self, h, a.space)
 
     def subtract(self, a, b, threshold=0, mode=_ffi.SUBTRACT_LIME):
         h, n = vp(), i64()

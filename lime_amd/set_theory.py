@@ -20,6 +20,9 @@ lime-core/src/main/scala/org/bdgenomics/lime/set_theory/:
     UnstrandedCluster / StrandedCluster / ...WithMinimumOverlap(rddToCompute,
                           partitionMap, threshold=0).compute()
         -> [(ReferenceRegion, [T])]                Cluster.scala:38-121
+    DistributedCoverage(rddToCompute, partitionMap).compute()
+        -> [(ReferenceRegion, depth)]              (no lime-core class: the
+                                                    CLI stub cli/Coverage.scala)
 
 An "RDD" here is any iterable of (ReferenceRegion, value) pairs held on the
 host.  `partitionMap` is accepted for signature parity and ignored: the
@@ -386,6 +389,39 @@ class DistributedComplement(_Op):
             out += [(ReferenceRegion(space.names[h["contig"][k]], int(h["start"][k]),
                                      int(h["end"][k])), []) for k in range(len(h["start"]))]
             A.close()
+        return out
+
+
+class DistributedCoverage(_Op):
+    """Depth of coverage: [(ReferenceRegion, depth)] for every maximal
+    interval of one contig on which the number of rows covering a base is
+    constant and >= 1 (bedtools genomecov -bg), contigs in RegionOrdering.
+    NOT a lime-core class: the reference only has the CLI stub
+    cli/Coverage.scala ("Compute the coverage over defined intervals"); the
+    name follows the mirror's Distributed* family.  Strand is ignored and the
+    regions are unstranded; zero-width rows add nothing; book-ended rows do
+    not change the depth where they touch."""
+
+    def __init__(self, rddToCompute, partitionMap=None, ctx=None):
+        super().__init__(ctx)
+        self.rdd = list(rddToCompute)
+        self.partitionMap = partitionMap
+
+    def compute(self):
+        regs, _ = _rows(self.rdd)
+        genome = _space_for(regs)
+        out = []
+        # contig-local: one space after the other
+        for space, rows in zip(genome.spaces, genome.split(regs, range(len(regs)))):
+            if not rows:
+                continue
+            A = self.ctx.set_from_host(space, *_arrays(space, regs, rows))
+            res = self.ctx.coverage(A)
+            h, d = res.to_host(), res.depths()
+            res.close()
+            A.close()
+            out += [(ReferenceRegion(space.names[h["contig"][k]], int(h["start"][k]),
+                                     int(h["end"][k])), int(d[k])) for k in range(len(d))]
         return out
 
 

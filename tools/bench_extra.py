@@ -31,6 +31,11 @@ the 8(f) rows (bench.py measures the headline config C2).  Single GPU; one JSON 
       tests): sort both + intersect (every pair filled through a 2^31-record
       buffer) + subtract in lime and set mode
 
+  coverage  depth-of-coverage runs (lime_coverage) of a sorted set: --input
+      pileup (C3's 5e8 rows) or uniform (1e8 rows as C2's A); the time of
+      merge on the same set and of the sort of the ends alone beside it, and
+      the depth_stats identity (sum of width x depth == sum of input widths)
+
 Inputs are generated on the device (counter-based RNG) outside the timed
 region; every step starts from unsorted rows in HBM.
 """
@@ -50,7 +55,9 @@ def main():
     p = argparse.ArgumentParser()
     p.add_argument("--workload", required=True,
                    choices=["c3", "c4", "c5", "bed", "closest", "closest_single", "window",
-                            "subtract", "b1_merge", "b1_pair"])
+                            "subtract", "b1_merge", "b1_pair", "coverage"])
+    p.add_argument("--input", choices=["pileup", "uniform"], default="pileup",
+                   help="coverage: C3's pile-up rows or uniform rows as C2's")
     p.add_argument("--steps", type=int, default=3)
     p.add_argument("--warmup", type=int, default=1)
     p.add_argument("--scale", type=float, default=1.0, help="row-count scale (testing)")
@@ -95,6 +102,7 @@ def main():
     if a.workload == "bed":
         bed_bench(a, ctx, space)
         return
+    step_ms = None  # a workload's own per-step time (device events), else the host clock's
     if a.workload == "c3":
         inp = gen(int(5e8 * a.scale), 0xC, 150, 600, pile=(2_000_000, 150))
         n = inp[0]
@@ -119,6 +127,48 @@ def main():
             return {"sort_ms": t0.elapsed_time(t1), "merge_ms": ms, "runs": runs}, \
                 {"kernel": "k_merge_scan (single pass, decoupled look-back)", "bound": "hbm",
                  "achieved": b / (ms * 1e-3) / 1e9, "alg_bytes": b}
+    elif a.workload == "coverage":
+        if a.input == "pileup":
+            inp = gen(int(5e8 * a.scale), 0xC, 150, 600, pile=(2_000_000, 150))
+            what = "C3's pile-up intervals (2e6 centres, N(0,150), len U[150,600])"
+        else:
+            inp = gen(int(1e8 * a.scale), 0xA, 50, 5000)
+            what = "uniform intervals over hg38 (len U[50,5000], as C2's)"
+        n = inp[0]
+        S = mkset(inp)  # (sorted outside the timed region: coverage takes a set)
+        widths = int((inp[3].to(torch.int64) - inp[2].to(torch.int64)).sum().item())
+
+        def step(rec):
+            t0 = ev()
+            r = ctx.coverage(S)
+            t1 = ev()
+            m = ctx.merge(S)
+            t2 = ev()
+            # the sort of the ends alone, as lime_coverage runs it: the set's
+            # ends as the starts of zero-width global rows
+            gs, ge, row = S.device_arrays()
+            E = ctx.set_from_global(space, n, ge, ge, row)
+            t3 = ev()
+            rec.append((t0, t1, t2, t3, r.n, r.depth_stats()))
+            for h in (E, m, r):
+                h.close()
+        units, unit = n, "intervals/s"
+        desc = f"coverage: depth runs of {n} sorted {what}"
+
+        def step_ms(recs):  # the rate is the coverage call's, not the comparisons'
+            return sum(r[0].elapsed_time(r[1]) for r in recs) / len(recs)
+
+        def roof(rec):
+            t0, t1, t2, t3, runs, (cov, db, mx) = rec[-1]
+            ms, sort_ms = t0.elapsed_time(t1), t2.elapsed_time(t3)
+            b = 16 * n + 12 * runs  # two walks over gs + sorted ends, the runs written
+            walk = max(ms - sort_ms, 1e-6)
+            return {"coverage_ms": ms, "merge_ms (same set)": t1.elapsed_time(t2),
+                    "sort_of_ends_ms": sort_ms, "sort_share": sort_ms / ms, "runs": runs,
+                    "covered_bases": cov, "depth_bases": db, "input_widths": widths,
+                    "depth_bases_equals_input_widths": db == widths, "max_depth": mx}, \
+                {"kernel": "k_cov count + fill (merge path over starts and sorted ends)",
+                 "bound": "hbm", "achieved": b / (walk * 1e-3) / 1e9, "alg_bytes": b}
     elif a.workload == "b1_merge":
         inp = gen(int(1e9 * a.scale), 0x1B, 150, 600, pile=(4_000_000, 150))
         n = inp[0]
@@ -372,6 +422,8 @@ def main():
         step(rec)
     torch.cuda.synchronize(dev)
     dt = (time.perf_counter() - t) / a.steps
+    if step_ms:
+        dt = step_ms(rec[-a.steps:]) * 1e-3
     br, rf = roof(rec)
     rf["peak"], rf["unit"] = HBM, "GB/s"
     rf["frac"] = rf["achieved"] / HBM
