@@ -71,6 +71,7 @@ typedef struct lime_result lime_result; /* merge / subtract / complement output 
 typedef struct lime_bed lime_bed;       /* parsed BED file (host memory)            */
 typedef struct lime_dbed lime_dbed;     /* parsed BED text (device memory)          */
 typedef struct lime_bitset lime_bitset; /* bit-per-base set over a space            */
+typedef struct lime_annot lime_annot;   /* per-row annotation of one set by another */
 
 /* One intersect output record: the intersection region in contig-local
  * coordinates (contig = contig of left row a_row) and the two input rows. */
@@ -303,6 +304,46 @@ int lime_result_depths(const lime_result *res, int64_t first, int64_t count, uin
 int lime_result_depth_device(const lime_result *res, const uint32_t **depth);
 int lime_result_depth_stats(const lime_result *res, uint64_t *covered_bases,
                             uint64_t *depth_bases, uint32_t *max_depth);
+/* Annotation of every row of a by b (bedtools coverage -a A -b B, intersect
+ * -c, annotate), without materialising a pair.  For a row a = [s, e) and the
+ * rows b of the same contig, under the strict half-open predicate of
+ * lime_intersect_count at threshold 0 (b.start < a.end && b.end > a.start;
+ * strand is not looked at, plain and stranded sets alike):
+ *   n_hits        the rows b that hit a: the records lime_intersect_count(a, b,
+ *                 0) has with this a_row;
+ *   covered       |a n union(b)| in bases: a's width minus the widths of the
+ *                 pieces lime_subtract(a, b, 0, LIME_SUBTRACT_SET) leaves it;
+ *   overlap_bases the sum over those records of end - start (u64);
+ *                 overlap_bases / width is the mean depth over a.
+ * Book-ended rows do not hit (0 hits).  A zero-width a strictly inside b, and
+ * a zero-width b strictly inside a, hit once and add nothing to covered or
+ * overlap_bases; a zero-width a at b's start or end, or at the point of a
+ * zero-width b, does not hit it.  A row ending at its contig's length never
+ * meets the next contig's rows.  One entry per row of a, in a's sorted order
+ * (lime_set_fill_host's); the handle owns its arrays and reads a until it is
+ * destroyed: destroy it before a.  Sets of different contexts or spaces:
+ * LIME_ERR_ARG. */
+int lime_annotate(lime_ctx *ctx, const lime_set *a, const lime_set *b, lime_annot **out);
+int64_t lime_annot_size(const lime_annot *an);
+/* entries [first, first + count) to host arrays, any of which may be NULL;
+ * row = the input row of a at that sorted position */
+int lime_annot_fill_host(const lime_annot *an, int64_t first, int64_t count, int64_t *row,
+                         uint32_t *n_hits, uint32_t *covered, uint64_t *overlap_bases);
+/* the device arrays (lime_annot_size entries each, owned by the handle) */
+int lime_annot_device_arrays(const lime_annot *an, const uint32_t **n_hits,
+                             const uint32_t **covered, const uint64_t **overlap_bases);
+/* one device reduction: rows with n_hits > 0, and the sums of the three
+ * columns (pairs = sum of n_hits = lime_intersect_count's n_pairs).  Any
+ * output may be NULL. */
+int lime_annot_totals(const lime_annot *an, uint64_t *rows_hit, uint64_t *pairs,
+                      uint64_t *covered, uint64_t *overlap_bases);
+/* "chrom<TAB>start<TAB>end<TAB>n_hits<TAB>covered<TAB>overlap_bases\n" per row
+ * of a in sorted order, formatted on the device; the two-call protocol of
+ * lime_set_format_bed.  Integers only: covered / (end - start) is the
+ * reader's to compute. */
+int lime_annot_format_bed(const lime_annot *an, const char *const *names, char *out, int64_t cap,
+                          int64_t *len);
+int lime_annot_destroy(lime_annot *an);
 /* Gaps of sorted, disjoint runs already in HBM (global coordinates, e.g. a
  * coordinate shard's merged runs after the cross-shard carry) over the genome,
  * keeping only the gaps whose START lies in [lo, hi) -- a shard's share of

@@ -13,6 +13,9 @@
 //   DistributedCoverage<T>(rdd, partitionMap).compute()
 //       -> vector<pair<ReferenceRegion, uint32_t>>            (depth runs; no lime-core
 //                                                              class, cli/Coverage.scala)
+//   DistributedAnnotate<T, U>(left, right, partitionMap).compute()
+//       -> vector<pair<ReferenceRegion, pair<T, Annot>>>       (every left row once: hits,
+//                                                              covered bases, overlap)
 //
 // An "RDD" is a host vector of (ReferenceRegion, value).  `partitionMap` is
 // accepted for signature parity and ignored: results equal the reference's
@@ -734,6 +737,74 @@ class DistributedCoverage {
 
    private:
     RDD<T> rdd_;
+    PartitionMap pm_;
+    Engine &eng_;
+};
+
+// What the right side does to one left row: the right rows that overlap it,
+// the bases of it they cover, and the sum of their overlaps.
+struct Annot {
+    uint32_t n_hits = 0, covered = 0;
+    uint64_t overlap_bases = 0;
+};
+
+// (leftRegion, (T, Annot)) for EVERY left row, once, in RegionOrdering of the
+// left side (bedtools coverage -a left -b right / intersect -c / annotate).
+// Not a lime-core class; the name follows the Distributed* family.  Strand as
+// DistributedIntersection: rows meet same-strand rows only; a left row whose
+// strand or contig group has no right rows gets zeros.
+template <class T, class U>
+class DistributedAnnotate {
+   public:
+    DistributedAnnotate(RDD<T> left, RDD<U> right, PartitionMap partitionMap = {},
+                        Engine &eng = Engine::thread_default())
+        : left_(std::move(left)), right_(std::move(right)), pm_(std::move(partitionMap)),
+          eng_(eng) {}
+
+    std::vector<std::pair<ReferenceRegion, std::pair<T, Annot>>> compute() {
+        auto gn = detail::join_space(left_, right_);
+        auto lg = detail::strand_groups(left_);
+        auto rg = detail::strand_groups(right_);
+        std::vector<Annot> val(left_.size());
+        for (auto &g : lg) {
+            auto it = rg.find(g.first);
+            if (it == rg.end()) continue;
+            auto ls = gn->split(left_, g.second), rs = gn->split(right_, it->second);
+            // contig-local: one space after the other
+            for (size_t q = 0; q < gn->spaces.size(); ++q) {
+                if (ls[q].empty() || rs[q].empty()) continue;
+                detail::SetHandle A, B;
+                detail::upload(eng_.ctx(), *gn->spaces[q], left_, ls[q], A);
+                detail::upload(eng_.ctx(), *gn->spaces[q], right_, rs[q], B);
+                lime_annot *an = nullptr;
+                check(lime_annotate(eng_.ctx(), A.h, B.h, &an));
+                const int64_t cnt = lime_annot_size(an);
+                std::vector<int64_t> row((size_t)cnt);
+                std::vector<uint32_t> h((size_t)cnt), c((size_t)cnt);
+                std::vector<uint64_t> o((size_t)cnt);
+                int rc = lime_annot_fill_host(an, 0, cnt, row.data(), h.data(), c.data(), o.data());
+                lime_annot_destroy(an);
+                check(rc);
+                for (int64_t k = 0; k < cnt; ++k) {
+                    Annot v;
+                    v.n_hits = h[k];
+                    v.covered = c[k];
+                    v.overlap_bases = o[k];
+                    val[ls[q][row[k]]] = v;
+                }
+            }
+        }
+        auto rank = detail::sorted_rank(left_);
+        std::vector<size_t> order(left_.size());
+        for (size_t i = 0; i < rank.size(); ++i) order[rank[i]] = i;
+        std::vector<std::pair<ReferenceRegion, std::pair<T, Annot>>> out;
+        for (size_t i : order) out.push_back({left_[i].first, {left_[i].second, val[i]}});
+        return out;
+    }
+
+   private:
+    RDD<T> left_;
+    RDD<U> right_;
     PartitionMap pm_;
     Engine &eng_;
 };

@@ -104,6 +104,13 @@ SIGNATURES = {
     "lime_result_depths": (C.c_int, [vp, i64, i64, P(u32)]),
     "lime_result_depth_device": (C.c_int, [vp, pp]),
     "lime_result_depth_stats": (C.c_int, [vp, P(u64), P(u64), P(u32)]),
+    "lime_annotate": (C.c_int, [vp, vp, vp, pp]),
+    "lime_annot_size": (i64, [vp]),
+    "lime_annot_fill_host": (C.c_int, [vp, i64, i64, P(i64), P(u32), P(u32), P(u64)]),
+    "lime_annot_device_arrays": (C.c_int, [vp, pp, pp, pp]),
+    "lime_annot_totals": (C.c_int, [vp, P(u64), P(u64), P(u64), P(u64)]),
+    "lime_annot_format_bed": (C.c_int, [vp, P(C.c_char_p), C.c_char_p, i64, P(i64)]),
+    "lime_annot_destroy": (C.c_int, [vp]),
     "lime_complement_runs": (C.c_int, [vp, vp, i64, vp, vp, i64, i64, pp, P(i64)]),
     "lime_result_size": (i64, [vp]),
     "lime_result_fill_host": (C.c_int, [vp, P(i32), P(i64), P(i64), P(i64), P(i64)]),

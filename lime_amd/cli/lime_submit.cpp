@@ -18,6 +18,11 @@
 //   coverage  A.bed             cli/Coverage.scala (a stub in the reference, not
 //                               registered by LimeMain): the depth runs as
 //                               bedGraph lines chrom, start, end, depth
+//   annotate  A.bed B.bed       no reference command (keys stranded, as
+//                               intersect): one line per row of A in sorted
+//                               order -- chrom, start, end, n_hits, covered,
+//                               overlap_bases, then the row's BED name field
+//                               if it has one
 //
 // Everything before "--" is accepted and ignored (there is no Spark).
 // Output is one region per line, tab-separated (chrom, start, end), followed
@@ -48,6 +53,7 @@ const Cmd kCommands[] = {
     {"cluster", "Cluster (but don't merge) overlapping/nearby intervals"},
     {"closest", "Find the closest region in the second input for each region of the first"},
     {"coverage", "Compute the coverage over defined intervals"},
+    {"annotate", "Count the hits, covered bases and overlap of the second input on each region of the first"},
 };
 
 void usage() {
@@ -167,6 +173,18 @@ int run(const std::vector<std::string> &args) {
         for (auto &o : out) {
             print_region(o.first);
             printf("\t%u\n", o.second);
+        }
+    } else if (cmd == "annotate") {
+        need(2);
+        auto out = DistributedAnnotate<std::string, std::string>(load_bed(args[1], true),
+                                                                 load_bed(args[2], true))
+                       .compute();
+        for (auto &o : out) {
+            const Annot &v = o.second.second;
+            print_region(o.first);
+            printf("\t%u\t%u\t%llu", v.n_hits, v.covered, (unsigned long long)v.overlap_bases);
+            if (!o.second.first.empty()) printf("\t%s", o.second.first.c_str());
+            printf("\n");
         }
     } else if (cmd == "complement") {
         need(2);

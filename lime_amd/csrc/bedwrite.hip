@@ -2,7 +2,8 @@
 // side of SURVEY.md 8(f) row 1; the reference prints each record through
 // Spark collect() + println, cli/*.scala).  Rows in GLOBAL coordinates of a
 // space (a sorted set, or a merge / subtract / complement result) become
-// "chrom<TAB>start<TAB>end[<TAB>extra]\n" lines, in row order.
+// "chrom<TAB>start<TAB>end[<TAB>extra]\n" lines, in row order (an annotation:
+// three integer columns after the region, the last one u64).
 //
 // Kernels (byte output, HBM / PCIe-bound):
 //   k_fmt_len    per row: contig by a search of the LDS-staged offsets,
@@ -29,9 +30,20 @@ struct FmtArgs {
     int32_t nc;
     const char *names;    // concatenated contig names
     const uint32_t *name_off;  // n_contigs + 1 byte offsets into names
+    const uint32_t *extra2;    // annotations: a second u32 column and a u64
+    const uint64_t *extra64;   // column after `extra` (null otherwise)
 };
 
 __device__ __forceinline__ int ndigits(uint32_t v) {
+    int d = 1;
+    while (v >= 10) {
+        v /= 10;
+        ++d;
+    }
+    return d;
+}
+
+__device__ __forceinline__ int ndigits64(uint64_t v) {
     int d = 1;
     while (v >= 10) {
         v /= 10;
@@ -65,6 +77,8 @@ __device__ __forceinline__ uint32_t line_len(const FmtArgs &a, const uint32_t *o
     e = a.ge[i] - off[c];
     uint32_t len = (a.name_off[c + 1] - a.name_off[c]) + 1 + ndigits(s) + 1 + ndigits(e) + 1;
     if (a.extra) len += 1 + ndigits(a.extra[i]);
+    if (a.extra2) len += 1 + ndigits(a.extra2[i]);
+    if (a.extra64) len += 1 + ndigits64(a.extra64[i]);
     return len;
 }
 
@@ -88,6 +102,15 @@ __device__ __forceinline__ int put_uint(char *p, uint32_t v) {
     return d;
 }
 
+__device__ __forceinline__ int put_uint64(char *p, uint64_t v) {
+    const int d = ndigits64(v);
+    for (int k = d - 1; k >= 0; --k) {
+        p[k] = (char)('0' + v % 10);
+        v /= 10;
+    }
+    return d;
+}
+
 // the line of row i at p (p in LDS or global)
 __device__ __forceinline__ void put_line(const FmtArgs &a, char *p, int c, uint32_t s, uint32_t e,
                                          int64_t i) {
@@ -100,6 +123,14 @@ __device__ __forceinline__ void put_line(const FmtArgs &a, char *p, int c, uint3
     if (a.extra) {
         *p++ = '\t';
         p += put_uint(p, a.extra[i]);
+    }
+    if (a.extra2) {
+        *p++ = '\t';
+        p += put_uint(p, a.extra2[i]);
+    }
+    if (a.extra64) {
+        *p++ = '\t';
+        p += put_uint64(p, a.extra64[i]);
     }
     *p = '\n';
 }
@@ -146,7 +177,7 @@ __global__ __launch_bounds__(WB) void k_fmt_write(FmtArgs a, const uint64_t *__r
 int format_bed(lime_ctx *ctx, const std::vector<uint32_t> &off,
                const std::vector<std::string> &names, int64_t n, const uint32_t *gs,
                const uint32_t *ge, const uint32_t *extra, char *out, int64_t cap,
-               int64_t *total_len) {
+               int64_t *total_len, const uint32_t *extra2, const uint64_t *extra64) {
     const int32_t nc = (int32_t)names.size();
     if ((int32_t)off.size() != nc + 1) return fail(LIME_ERR_ARG, "names do not match the space");
     std::string cat;
@@ -166,7 +197,7 @@ int format_bed(lime_ctx *ctx, const std::vector<uint32_t> &off,
     LIME_HIP(hipMemcpyAsync(d_noff, noff.data(), 4 * noff.size(), hipMemcpyHostToDevice, S(ctx)));
     if (!cat.empty())
         LIME_HIP(hipMemcpyAsync(d_names, cat.data(), cat.size(), hipMemcpyHostToDevice, S(ctx)));
-    FmtArgs a{gs, ge, extra, n, d_off, nc, d_names, d_noff};
+    FmtArgs a{gs, ge, extra, n, d_off, nc, d_names, d_noff, extra2, extra64};
     uint64_t total = 0;
     if (n > 0) {
         hipLaunchKernelGGL(k_fmt_len, dim3(blocks_for(n, WB)), dim3(WB), 0, S(ctx), a, len);

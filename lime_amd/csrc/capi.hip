@@ -223,6 +223,12 @@ lime_result::~lime_result() {
     lime::release(ctx, depth);
 }
 
+lime_annot::~lime_annot() {
+    lime::release(ctx, n_hits);
+    lime::release(ctx, covered);
+    lime::release(ctx, overlap);
+}
+
 void lime_bitset::drop_bins() {
     for (auto &b : bins) {
         lime::release(ctx, b.slab2);
@@ -1114,6 +1120,92 @@ int lime_result_depth_stats(const lime_result *r, uint64_t *covered_bases, uint6
     if (!r->depth) return fail(LIME_ERR_ARG, "not a coverage result");
     hipSetDevice(r->ctx->device);
     return depth_stats(r->ctx, r, covered_bases, depth_bases, max_depth);
+}
+
+// ---------------------------------------------------------------- annotate
+static int names_of(const char *const *names, int32_t n, std::vector<std::string> &v);
+
+int lime_annotate(lime_ctx *ctx, const lime_set *a, const lime_set *b, lime_annot **out) {
+    if (!ctx || !a || !b || !out) return fail(LIME_ERR_ARG, "bad annotate arguments");
+    if (!same_space(a, b)) return fail(LIME_ERR_ARG, "sets live in different coordinate spaces");
+    LIME_TRY(same_ctx(ctx, a));
+    LIME_TRY(same_ctx(ctx, b));
+    if (a->min_shift || b->min_shift) return fail(LIME_ERR_ARG, "annotate needs fully sorted sets");
+    hipSetDevice(ctx->device);
+    std::unique_ptr<lime_annot> r(new lime_annot());
+    r->ctx = ctx;
+    r->a = a;
+    LIME_TRY(annotate_run(ctx, a, b, r.get()));
+    *out = r.release();
+    return LIME_OK;
+}
+
+int64_t lime_annot_size(const lime_annot *an) { return an ? an->n : -1; }
+
+int lime_annot_fill_host(const lime_annot *an, int64_t first, int64_t count, int64_t *row,
+                         uint32_t *n_hits, uint32_t *covered, uint64_t *overlap_bases) {
+    if (!an) return fail(LIME_ERR_ARG, "annotation is null");
+    if (first < 0 || count < 0 || first + count > an->n)
+        return fail(LIME_ERR_ARG, "range outside the annotation");
+    lime_ctx *ctx = an->ctx;
+    hipSetDevice(ctx->device);
+    if (count == 0) return LIME_OK;
+    const size_t c = (size_t)count;
+    std::vector<uint32_t> rw;
+    if (row) {
+        rw.resize(c);
+        LIME_HIP(hipMemcpyAsync(rw.data(), an->a->row + first, 4 * c, hipMemcpyDeviceToHost,
+                                S(ctx)));
+    }
+    if (n_hits)
+        LIME_HIP(hipMemcpyAsync(n_hits, an->n_hits + first, 4 * c, hipMemcpyDeviceToHost, S(ctx)));
+    if (covered)
+        LIME_HIP(hipMemcpyAsync(covered, an->covered + first, 4 * c, hipMemcpyDeviceToHost,
+                                S(ctx)));
+    if (overlap_bases)
+        LIME_HIP(hipMemcpyAsync(overlap_bases, an->overlap + first, 8 * c, hipMemcpyDeviceToHost,
+                                S(ctx)));
+    LIME_HIP(hipStreamSynchronize(S(ctx)));
+    if (row)
+        for (size_t i = 0; i < c; ++i) row[i] = rw[i];
+    return LIME_OK;
+}
+
+int lime_annot_device_arrays(const lime_annot *an, const uint32_t **n_hits,
+                             const uint32_t **covered, const uint64_t **overlap_bases) {
+    if (!an) return fail(LIME_ERR_ARG, "annotation is null");
+    if (n_hits) *n_hits = an->n_hits;
+    if (covered) *covered = an->covered;
+    if (overlap_bases) *overlap_bases = an->overlap;
+    return LIME_OK;
+}
+
+int lime_annot_totals(const lime_annot *an, uint64_t *rows_hit, uint64_t *pairs,
+                      uint64_t *covered, uint64_t *overlap_bases) {
+    if (!an) return fail(LIME_ERR_ARG, "annotation is null");
+    hipSetDevice(an->ctx->device);
+    uint64_t h[4];
+    LIME_TRY(annot_totals(an->ctx, an, h));
+    if (rows_hit) *rows_hit = h[0];
+    if (pairs) *pairs = h[1];
+    if (covered) *covered = h[2];
+    if (overlap_bases) *overlap_bases = h[3];
+    return LIME_OK;
+}
+
+int lime_annot_format_bed(const lime_annot *an, const char *const *names, char *out, int64_t cap,
+                          int64_t *len) {
+    if (!an || !len) return fail(LIME_ERR_ARG, "bad format arguments");
+    std::vector<std::string> nm;
+    LIME_TRY(names_of(names, an->a->n_contigs, nm));
+    hipSetDevice(an->ctx->device);
+    return format_bed(an->ctx, an->a->off, nm, an->n, an->a->gs, an->a->ge, an->n_hits, out, cap,
+                      len, an->covered, an->overlap);
+}
+
+int lime_annot_destroy(lime_annot *an) {
+    delete an;
+    return LIME_OK;
 }
 
 int lime_complement(lime_ctx *ctx, const lime_space *genome, const lime_set *a, lime_result **out,

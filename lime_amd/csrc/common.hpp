@@ -204,6 +204,21 @@ struct lime_bitset {
     int64_t nt = 0;  // paint tiles of the bins
 };
 
+// Per-row annotation of A against B (annotate.hip), in A's sorted order.
+// Owns its three arrays (released by the destructor); a is borrowed.
+struct lime_annot {
+    lime_annot() = default;
+    lime_annot(const lime_annot &) = delete;
+    lime_annot &operator=(const lime_annot &) = delete;
+    ~lime_annot();
+    lime_ctx *ctx = nullptr;
+    int64_t n = 0;
+    uint32_t *n_hits = nullptr;   // rows of B that hit the row
+    uint32_t *covered = nullptr;  // bases of the row inside the union of B
+    uint64_t *overlap = nullptr;  // sum of overlapsBy over those rows of B
+    const lime_set *a = nullptr;
+};
+
 static_assert(!std::is_copy_constructible<lime_set>::value, "lime_set owns pool blocks");
 static_assert(!std::is_copy_constructible<lime_result>::value, "lime_result owns pool blocks");
 static_assert(!std::is_copy_constructible<lime_bitset>::value, "lime_bitset owns pool blocks");
@@ -335,6 +350,14 @@ int coverage_run(lime_ctx *ctx, const lime_set *set, lime_result *res);
 // sum of widths, sum of width x depth and maximum depth of a coverage result
 int depth_stats(lime_ctx *ctx, const lime_result *res, uint64_t *covered, uint64_t *depth_bases,
                 uint32_t *max_depth);
+// a set's ends sorted ascending, as the starts of the temporary set *ends
+// (coverage.hip; the caller's, empty on entry)
+int sorted_ends(lime_ctx *ctx, const lime_set *set, lime_set *ends);
+// per-row hits, covered bases and overlap of A against B (annotate.hip); out
+// owns its three arrays
+int annotate_run(lime_ctx *ctx, const lime_set *A, const lime_set *B, lime_annot *out);
+// rows with a hit, sum of n_hits, of covered, of overlap over an annotation
+int annot_totals(lime_ctx *ctx, const lime_annot *an, uint64_t h[4]);
 int complement_run(lime_ctx *ctx, const lime_result *runs, const uint32_t *d_off,
                    const uint32_t *d_len, int32_t nc, lime_result *res, uint32_t wlo = 0,
                    uint32_t whi = 0xffffffffu);
@@ -362,7 +385,8 @@ int closest_rounds(const ClosestPlan *pl, bool *sequential);
 int format_bed(lime_ctx *ctx, const std::vector<uint32_t> &off,
                const std::vector<std::string> &names, int64_t n, const uint32_t *gs,
                const uint32_t *ge, const uint32_t *extra, char *out, int64_t cap,
-               int64_t *total_len);
+               int64_t *total_len, const uint32_t *extra2 = nullptr,
+               const uint64_t *extra64 = nullptr);
 int bitset_build(lime_ctx *ctx, const lime_set *a, lime_bitset *bs);
 int bitset_build_rows(lime_ctx *ctx, const lime_space *sp, int64_t n, const int32_t *d_contig,
                       const uint32_t *d_start, const uint32_t *d_end, const uint32_t *d_off,

@@ -262,6 +262,20 @@ __global__ __launch_bounds__(256) void k_depth_stats(const uint32_t *__restrict_
 
 }  // namespace
 
+// E of a set: its ends sorted ascending, as the starts of a temporary set of
+// zero-width rows (ge, ge) (the caller's, empty on entry: its blocks go back
+// to the pool when it dies).  Shared with annotate.hip: the keys-only sort of
+// the ends lands here.
+int sorted_ends(lime_ctx *ctx, const lime_set *set, lime_set *ends) {
+    ends->ctx = ctx;
+    ends->n = set->n;
+    ends->n_contigs = set->n_contigs;
+    ends->off = set->off;
+    ends->len = set->len;
+    ends->d_off = set->d_off;
+    return sort_set_global(ctx, ends, set->ge, set->ge, set->row, nullptr);
+}
+
 // depth runs of a sorted set; the result owns gs / ge / depth
 int coverage_run(lime_ctx *ctx, const lime_set *set, lime_result *res) {
     const int64_t n = set->n;
@@ -272,16 +286,10 @@ int coverage_run(lime_ctx *ctx, const lime_set *set, lime_result *res) {
         LIME_TRY(alloc(ctx, &res->depth, 1));
         return LIME_OK;
     }
-    // E: the ends sorted ascending, as the starts of a temporary set of
-    // zero-width rows (ge, ge); released when `ends` dies, on every path
+    // E: the ends sorted ascending (sorted_ends); released when `ends` dies,
+    // on every path
     lime_set ends;
-    ends.ctx = ctx;
-    ends.n = n;
-    ends.n_contigs = set->n_contigs;
-    ends.off = set->off;
-    ends.len = set->len;
-    ends.d_off = set->d_off;
-    LIME_TRY(sort_set_global(ctx, &ends, set->ge, set->ge, set->row, nullptr));
+    LIME_TRY(sorted_ends(ctx, set, &ends));
     const int64_t nt = (2 * n + CV_TILE - 1) / CV_TILE;
     PoolPtr<uint32_t> split, cnt, tbase, total;
     LIME_TRY(split.alloc(ctx, (size_t)nt + 1));

@@ -280,6 +280,67 @@ class Result:
             pass
 
 
+class Annotation:
+    """Per row of a, in a's sorted order: the rows of b that hit it, the bases
+    of it they cover and the sum of their overlaps (lime_annot)."""
+
+    def __init__(self, ctx, handle, a, keep=()):
+        # the handle reads a's device arrays: keep it alive
+        self.ctx, self._h, self.a, self.space, self._keep = ctx, handle, a, a.space, keep
+
+    @property
+    def n(self):
+        return int(_lib().lime_annot_size(self._h))
+
+    def fill_host(self, first=0, count=None):
+        """entries [first, first + count): row (a's input row), n_hits,
+        covered, overlap_bases"""
+        count = self.n - first if count is None else int(count)
+        m = max(count, 1)
+        out = {"row": np.zeros(m, np.int64), "n_hits": np.zeros(m, np.uint32),
+               "covered": np.zeros(m, np.uint32), "overlap_bases": np.zeros(m, np.uint64)}
+        check(_lib().lime_annot_fill_host(self._h, int(first), count, _ptr(out["row"], i64),
+                                          _ptr(out["n_hits"], u32), _ptr(out["covered"], u32),
+                                          _ptr(out["overlap_bases"], u64)))
+        return {k: v[:count] for k, v in out.items()}
+
+    def to_host(self):
+        """contig, start, end, row of every row of a with its n_hits, covered
+        and overlap_bases"""
+        out = self.a.to_host()
+        out.update(self.fill_host())
+        return out
+
+    def totals(self):
+        """(rows with a hit, sum of n_hits, sum of covered, sum of
+        overlap_bases) from one device reduction"""
+        v = [u64() for _ in range(4)]
+        check(_lib().lime_annot_totals(self._h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def device_arrays(self):
+        """device pointers of n_hits (u32), covered (u32), overlap_bases (u64)"""
+        v = [vp() for _ in range(3)]
+        check(_lib().lime_annot_device_arrays(self._h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def to_bed(self):
+        """chrom, start, end, n_hits, covered, overlap_bases per row of a,
+        formatted on the device"""
+        return _format_bed(_lib().lime_annot_format_bed, self._h, self.space)
+
+    def close(self):
+        if self._h and self.ctx.handle:  # a closed context already freed its pool
+            _lib().lime_annot_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Pairs:
     """Intersect plan: exact pair count plus chunked fill (lime_pairs)."""
 
@@ -516,6 +577,13 @@ class Context:
         h, n = vp(), i64()
         check(_lib().lime_coverage(self._h, a._h, C.byref(h), C.byref(n)))
         return Result(self, h, a.space)
+
+    def annotate(self, a, b):
+        """per row of a: the rows of b that hit it, the bases of it they
+        cover, the sum of their overlaps (Annotation), without pairs"""
+        h = vp()
+        check(_lib().lime_annotate(self._h, a._h, b._h, C.byref(h)))
+        return Annotation(self, h, a, keep=(a,))
 
     def subtract(self, a, b, threshold=0, mode=_ffi.SUBTRACT_LIME):
         h, n = vp(), i64()

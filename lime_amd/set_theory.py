@@ -23,6 +23,10 @@ lime-core/src/main/scala/org/bdgenomics/lime/set_theory/:
     DistributedCoverage(rddToCompute, partitionMap).compute()
         -> [(ReferenceRegion, depth)]              (no lime-core class: the
                                                     CLI stub cli/Coverage.scala)
+    DistributedAnnotate(leftRdd, rightRdd, partitionMap).compute()
+        -> [(leftRegion, (T, n_hits, covered, overlap_bases))]
+                                                   (no lime-core class: every
+                                                    left row once)
 
 An "RDD" here is any iterable of (ReferenceRegion, value) pairs held on the
 host.  `partitionMap` is accepted for signature parity and ignored: the
@@ -423,6 +427,51 @@ class DistributedCoverage(_Op):
             out += [(ReferenceRegion(space.names[h["contig"][k]], int(h["start"][k]),
                                      int(h["end"][k])), int(d[k])) for k in range(len(d))]
         return out
+
+
+class DistributedAnnotate(_Op):
+    """[(leftRegion, (T, n_hits, covered, overlap_bases))] for EVERY left row,
+    once, in RegionOrdering of the left side: the right rows that overlap it
+    (ReferenceRegion.overlaps: strict, same strand), the bases of it they
+    cover, and the sum of their overlaps (bedtools coverage -a left -b right /
+    intersect -c / annotate).  NOT a lime-core class; the name follows the
+    mirror's Distributed* family.  Strand as DistributedIntersection: rows
+    meet same-strand rows only; a left row whose strand or contig group has no
+    right rows gets zeros.  Contig-local, so a genome cut into several spaces
+    needs no chaining."""
+
+    def __init__(self, leftRdd, rightRdd, partitionMap=None, ctx=None):
+        super().__init__(ctx)
+        self.left, self.right = list(leftRdd), list(rightRdd)
+        self.partitionMap = partitionMap
+
+    def compute(self):
+        lr, lv = _rows(self.left)
+        rr, _ = _rows(self.right)
+        genome = _space_for(lr, rr)
+        lg, rg = _strand_groups(lr), _strand_groups(rr)
+        val = np.zeros((len(lr), 3), dtype=np.uint64)
+        for strand, lrows_all in lg.items():
+            rrows_all = rg.get(strand)
+            if not rrows_all:
+                continue
+            for space, lrows, rrows in zip(genome.spaces, genome.split(lr, lrows_all),
+                                           genome.split(rr, rrows_all)):
+                if not lrows or not rrows:
+                    continue
+                A = self.ctx.set_from_host(space, *_arrays(space, lr, lrows))
+                B = self.ctx.set_from_host(space, *_arrays(space, rr, rrows))
+                an = self.ctx.annotate(A, B)
+                h = an.fill_host()
+                an.close()
+                A.close()
+                B.close()
+                rows = np.asarray(lrows, dtype=np.int64)[h["row"]]
+                val[rows, 0] = h["n_hits"]
+                val[rows, 1] = h["covered"]
+                val[rows, 2] = h["overlap_bases"]
+        order = np.argsort(_sorted_rank(lr))
+        return [(lr[i], (lv[i], int(val[i, 0]), int(val[i, 1]), int(val[i, 2]))) for i in order]
 
 
 class _Cluster(_Op):

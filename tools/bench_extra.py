@@ -36,6 +36,11 @@ the 8(f) rows (bench.py measures the headline config C2).  Single GPU; one JSON 
       merge on the same set and of the sort of the ends alone beside it, and
       the depth_stats identity (sum of width x depth == sum of input widths)
 
+  annotate  per-row hits, covered bases and overlap (lime_annotate) of C2's A
+      by C2's B (2 x 1e8 rows, seeds 0xA / 0xB, sorted outside the timed
+      region), the intersect count pass on the same sets beside it, and the
+      identity sum(n_hits) == the plan's pair count
+
 Inputs are generated on the device (counter-based RNG) outside the timed
 region; every step starts from unsorted rows in HBM.
 """
@@ -55,7 +60,7 @@ def main():
     p = argparse.ArgumentParser()
     p.add_argument("--workload", required=True,
                    choices=["c3", "c4", "c5", "bed", "closest", "closest_single", "window",
-                            "subtract", "b1_merge", "b1_pair", "coverage"])
+                            "subtract", "b1_merge", "b1_pair", "coverage", "annotate"])
     p.add_argument("--input", choices=["pileup", "uniform"], default="pileup",
                    help="coverage: C3's pile-up rows or uniform rows as C2's")
     p.add_argument("--steps", type=int, default=3)
@@ -169,6 +174,47 @@ def main():
                     "depth_bases_equals_input_widths": db == widths, "max_depth": mx}, \
                 {"kernel": "k_cov count + fill (merge path over starts and sorted ends)",
                  "bound": "hbm", "achieved": b / (walk * 1e-3) / 1e9, "alg_bytes": b}
+    elif a.workload == "annotate":
+        na = nb_ = int(1e8 * a.scale)
+        A_in, B_in = gen(na, 0xA, 50, 5000), gen(nb_, 0xB, 50, 5000)
+        A, B = mkset(A_in), mkset(B_in)  # (sorted outside the timed region)
+        n = na
+
+        def step(rec):
+            t0 = ev()
+            an = ctx.annotate(A, B)
+            t1 = ev()
+            plan = ctx.intersect(A, B)  # the count pass alone: the grand total only
+            t2 = ev()
+            rec.append((t0, t1, t2, an.totals(), plan.n))
+            plan.close()
+            an.close()
+        units, unit = n, "rows of A/s"
+        desc = f"annotate: hits, covered bases and overlap of {na} rows by {nb_} rows (C2's " \
+               "sets, uniform over hg38, len U[50,5000])"
+
+        def step_ms(recs):
+            return sum(r[0].elapsed_time(r[1]) for r in recs) / len(recs)
+
+        def roof(rec):
+            t0, t1, t2, (rows_hit, pairs, cov, ov), n_pairs = rec[-1]
+            ms = t0.elapsed_time(t1)
+            m = ctx.merge(B)
+            nr = m.n
+            m.close()
+            # per row of B: the sort of the ends (sort.hip's budget for a 12-B
+            # row is not counted), S and E widened (4 + 8) and scanned (8 + 8
+            # + 8) twice, merge (8), both staged once by k_annotate (8); per
+            # run 8 written, widths 8 + 4, scan 12, staged 4; per row of A 8
+            # read and 16 written; the gathers (4 x 8 B + up to 6 x 4 B per row
+            # of A, mostly cache hits) are not counted
+            b = nb_ * (2 * (12 + 24) + 8 + 8) + nr * 36 + na * 24
+            return {"annotate_ms": ms, "intersect_count_ms (same sets)": t1.elapsed_time(t2),
+                    "rows_hit": rows_hit, "pairs": pairs, "covered_bases": cov,
+                    "overlap_bases": ov, "intersect_n_pairs": n_pairs,
+                    "pairs_equals_intersect_count": pairs == n_pairs, "runs_of_b": nr}, \
+                {"kernel": "lime_annotate (sort of ends, scans, merge, k_ann_split, k_annotate)",
+                 "bound": "hbm", "achieved": b / (ms * 1e-3) / 1e9, "alg_bytes": b}
     elif a.workload == "b1_merge":
         inp = gen(int(1e9 * a.scale), 0x1B, 150, 600, pile=(4_000_000, 150))
         n = inp[0]
