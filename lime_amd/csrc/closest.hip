@@ -60,9 +60,9 @@ struct ClosestPlan {
     lime_ctx *ctx = nullptr;
     const lime_set *A = nullptr, *B = nullptr;
     int64_t nl = 0;
-    uint32_t *jp = nullptr;    // per left: right pointer j after the left
+    uint32_t *jp = nullptr;    // per left: right pointer j after the left (0: no output)
     uint32_t *pp = nullptr;    // per left: cache head p after the left
-    uint32_t *dd = nullptr;    // per left: D (0xffffffff: no output)
+    uint32_t *dd = nullptr;    // per left: D (any u32: 0xffffffff is a distance a full span has)
     uint64_t *off = nullptr;   // per left: exclusive output offsets
     uint32_t *rb = nullptr;    // n_contigs + 1 right contig bounds
     uint32_t *aa = nullptr;    // per left: A, the first right starting at or after its end
@@ -332,12 +332,14 @@ __global__ __launch_bounds__(CB) void k_fresh(Lefts L, Rights R, State s,
     const int c = contig_of(o, L.nc, ls);
     const int64_t r0 = L.rb[c];
     const int64_t j = pointer_of(s, c, i);
-    jp[i] = (uint32_t)j;
     if (!s.live[c] || j <= r0) {
+        // no output: a left with output has j > r0 >= 0, so j = 0 marks it
+        jp[i] = 0u;
         dd[i] = NONE;
         P[i] = (uint32_t)r0;
         return;
     }
+    jp[i] = (uint32_t)j;
     const uint32_t D = udist(ls, le, R.gs[j - 1], R.ge[j - 1]);
     dd[i] = D;
     P[i] = (uint32_t)near_from(R, ls, le, D, s.A[i], j, r0, true);
@@ -359,13 +361,13 @@ __global__ __launch_bounds__(CB) void k_prune_round(Lefts L, Rights R, State s,
     if (i >= L.n) return;
     const uint32_t cur = pin[i];
     uint32_t nv = cur;
-    const uint32_t D = dd[i];
-    if (D != NONE) {
-        const uint32_t ls = L.gs[i], le = L.ge[i];
+    const uint32_t j = jp[i];
+    if (j != 0u) {
+        const uint32_t ls = L.gs[i], le = L.ge[i], D = dd[i];
         const int c = contig_of(o, L.nc, ls);
         const int64_t r0 = L.rb[c];
         const int64_t x = max((int64_t)(i > 0 ? pin[i - 1] : 0u), r0);
-        const int64_t f = near_from(R, ls, le, D, s.A[i], jp[i], x, false);
+        const int64_t f = near_from(R, ls, le, D, s.A[i], j, x, false);
         nv = (uint32_t)max((int64_t)cur, f);
     }
     pout[i] = nv;
@@ -390,9 +392,9 @@ __global__ __launch_bounds__(CB) void k_seq_prune(Lefts L, Rights R, State s,
     int64_t prev = r0;
     for (int64_t i = i0; i < i1; ++i) {
         int64_t v = p[i];
-        const uint32_t D = dd[i];
-        if (D != NONE) {
-            const int64_t f = near_from(R, L.gs[i], L.ge[i], D, s.A[i], jp[i], max(prev, r0),
+        const uint32_t j = jp[i];
+        if (j != 0u) {
+            const int64_t f = near_from(R, L.gs[i], L.ge[i], dd[i], s.A[i], j, max(prev, r0),
                                         false);
             v = max(v, f);
             p[i] = (uint32_t)v;
@@ -479,8 +481,10 @@ __global__ __launch_bounds__(64) void k_seq_single(Lefts L, Rights R,
     }
 }
 
-// lefts of contigs the sweep never enters: no output
+// lefts of contigs the sweep never enters: no output (after k_last has read
+// the exit pointers)
 __global__ __launch_bounds__(CB) void k_kill(Lefts L, const uint8_t *__restrict__ live,
+                                             uint32_t *__restrict__ jp,
                                              uint32_t *__restrict__ dd) {
     __shared__ uint32_t s_off[OCAP];
     if (L.nc + 1 <= OCAP)
@@ -489,7 +493,10 @@ __global__ __launch_bounds__(CB) void k_kill(Lefts L, const uint8_t *__restrict_
     const uint32_t *o = L.nc + 1 <= OCAP ? s_off : L.off;
     const int64_t i = (int64_t)blockIdx.x * CB + threadIdx.x;
     if (i >= L.n) return;
-    if (!live[contig_of(o, L.nc, L.gs[i])]) dd[i] = NONE;
+    if (!live[contig_of(o, L.nc, L.gs[i])]) {
+        jp[i] = 0u;
+        dd[i] = NONE;
+    }
 }
 
 // Output pass.  A match is k in [p, j) with dist(L, R[k]) == D.
@@ -540,7 +547,7 @@ __global__ __launch_bounds__(CB) void k_scan(Lefts L, Rights R, EndIndex E,
     const int64_t i = ((int64_t)blockIdx.x * (CB / 64) + threadIdx.x / 64) * 64 + lane;
     if (USEWIN) {
         uint32_t lo = 0xffffffffu, hi = 0;
-        if (i < L.n && dd[i] == 0u) {
+        if (i < L.n && jp[i] != 0u && dd[i] == 0u) {
             lo = pp[i];
             hi = min(jp[i], E.aa[i]);
         }
@@ -568,7 +575,7 @@ __global__ __launch_bounds__(CB) void k_scan(Lefts L, Rights R, EndIndex E,
     __syncthreads();
     uint32_t ls = 0, le = 0, D = NONE, p = 0, j = 0, s0 = 0, e0 = 0, ar = 0;
     uint64_t pos0 = 0;
-    bool valid = i < L.n && dd[i] != NONE;
+    bool valid = i < L.n && jp[i] != 0u;  // (D itself may be any u32: 0xffffffff is a distance)
     if (valid) {
         ls = L.gs[i];
         le = L.ge[i];
@@ -858,7 +865,7 @@ int plan_body(lime_ctx *ctx, const lime_set *A, const lime_set *B, int mode, Clo
     State s{Aa, U, stuck, live};
     if (mode != 0) {
         hipLaunchKernelGGL(k_kill, dim3(gl), dim3(CB), 0, S(ctx), L, (const uint8_t *)live,
-                           pl->dd);
+                           pl->jp, pl->dd);
         LIME_HIP(hipGetLastError());
     } else {
         hipLaunchKernelGGL(k_fresh, dim3(gl), dim3(CB), 0, S(ctx), L, R, s, pl->jp, pl->dd, P);
