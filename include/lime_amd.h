@@ -46,7 +46,10 @@ extern "C" {
 /* 2: lime_set_lower_bound / _first_reaching return -(LIME_ERR_*) on error
  *    (was -1); lime_pairs_checksum_device and the sharded-path helpers added
  * 6: lime_route_rows_interleaved, lime_deinterleave_u32 (the routed
- *    exchange without per-column repacking) */
+ *    exchange without per-column repacking)
+ *    (additions since, none changing an existing entry point: lime_coverage,
+ *    lime_annotate and their accessors; lime_multiinter, lime_result_masks,
+ *    lime_result_mask_device) */
 #define LIME_ABI_VERSION 6
 
 /* status codes */
@@ -304,6 +307,33 @@ int lime_result_depths(const lime_result *res, int64_t first, int64_t count, uin
 int lime_result_depth_device(const lime_result *res, const uint32_t **depth);
 int lime_result_depth_stats(const lime_result *res, uint64_t *covered_bases,
                             uint64_t *depth_bases, uint32_t *max_depth);
+/* k sets at once (1 <= k <= 32, one context, one space; plain and stranded
+ * alike, strand ignored; the same set may appear twice and then holds two
+ * bits).  mask(p) has bit i set iff some row of sets[i] has start <= p < end.
+ *   min_sets == 0       membership (bedtools multiinter): every maximal
+ *                       interval inside one contig on which mask is constant
+ *                       and non-zero, with its mask and n_sets = popcount(mask);
+ *                       [0,5) in sets[0] and [5,9) in sets[1] give two runs,
+ *                       masks 1 and 2
+ *   1 <= min_sets <= k  consensus: every maximal interval inside one contig
+ *                       on which popcount(mask) >= min_sets (neighbouring
+ *                       pieces of different masks coalesced); min_sets == 1 is
+ *                       the union of all rows, min_sets == k the per-base k-way
+ *                       AND (the runs of lime_bitset_and_runs)
+ * Contigs in String order, ascending inside a contig; zero-width rows add
+ * nothing; a run never crosses contigs.  A membership result carries n_sets in
+ * the depth column: lime_result_depths / _depth_device / _depth_stats work on
+ * it (covered_bases = the union of all sets, depth_bases = the sum over the
+ * sets of each set's union, max_depth = the largest n_sets); a consensus result
+ * is a plain result.  k outside [1, 32], a null set, min_sets outside [0, k],
+ * sets of different contexts or spaces: LIME_ERR_ARG.  More than 2^32 - 1 ends
+ * of the sets' merged runs: LIME_ERR_OVERFLOW. */
+int lime_multiinter(lime_ctx *ctx, int32_t k, const lime_set *const *sets, int32_t min_sets,
+                    lime_result **out, int64_t *n_runs);
+/* membership results only (LIME_ERR_ARG otherwise): masks of runs [first,
+ * first + count) to a host array; the device array (owned by the result) */
+int lime_result_masks(const lime_result *res, int64_t first, int64_t count, uint32_t *mask);
+int lime_result_mask_device(const lime_result *res, const uint32_t **mask);
 /* Annotation of every row of a by b (bedtools coverage -a A -b B, intersect
  * -c, annotate), without materialising a pair.  For a row a = [s, e) and the
  * rows b of the same contig, under the strict half-open predicate of
@@ -359,7 +389,7 @@ int lime_complement_runs(lime_ctx *ctx, const lime_space *genome, int64_t n,
 int64_t lime_result_size(const lime_result *res);
 /* Host copy of a result: regions in contig-local coordinates plus the
  * left/right input rows (-1 where the reference has None / no payload, and
- * for every run of a coverage result). */
+ * for every run of a coverage or multiinter result). */
 int lime_result_fill_host(const lime_result *res, int32_t *contig, int64_t *start, int64_t *end,
                           int64_t *a_row, int64_t *b_row);
 /* merge only: run index of every input row (the Iterable[T] grouping). */
@@ -396,7 +426,9 @@ int lime_result_checksum(const lime_result *res, uint64_t *reg_sum, uint64_t *re
  * caller-owned HOST buffer.  names[c] = name of contig c of the object's
  * space (String order).  Two-call protocol: with cap < *len (e.g. out =
  * NULL, cap = 0) only the byte count *len is returned.  A coverage result
- * writes "chrom<TAB>start<TAB>end<TAB>depth\n" (a bedGraph). */
+ * writes "chrom<TAB>start<TAB>end<TAB>depth\n" (a bedGraph), a membership
+ * result "chrom<TAB>start<TAB>end<TAB>n_sets<TAB>mask\n" (the mask in
+ * decimal, bit i = sets[i]), a consensus result three columns. */
 int lime_set_format_bed(const lime_set *set, const char *const *names, char *out, int64_t cap,
                         int64_t *len);
 int lime_result_format_bed(const lime_result *res, const char *const *names, char *out,

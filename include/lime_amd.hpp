@@ -741,6 +741,105 @@ class DistributedCoverage {
     Engine &eng_;
 };
 
+// The sets that cover one membership run: bit i of mask = the i-th input.
+struct Membership {
+    uint32_t n_sets = 0, mask = 0;
+};
+
+// 1 to 32 inputs at once (bedtools multiinter).  min_sets = 0: (region,
+// Membership) for every maximal interval of one contig on which the set of
+// inputs covering a base is constant and not empty.  1 <= min_sets <= k: the
+// maximal intervals covered by at least min_sets of the inputs (Membership
+// {0, 0}).  Contigs in RegionOrdering; strand is ignored, the regions are
+// unstranded.  Not a lime-core class; the name follows the Distributed* family.
+// Contig-local: a genome cut into several spaces runs one after the other.
+template <class T>
+class DistributedMultiIntersection {
+   public:
+    DistributedMultiIntersection(std::vector<RDD<T>> rdds, int min_sets = 0,
+                                 Engine &eng = Engine::thread_default())
+        : rdds_(std::move(rdds)), min_sets_(min_sets), eng_(eng) {}
+
+    std::vector<std::pair<ReferenceRegion, Membership>> compute() {
+        std::vector<std::pair<ReferenceRegion, Membership>> out;
+        each_space([&](const detail::Space &sp, lime_result *res, int64_t cnt) {
+            std::vector<int32_t> c((size_t)cnt);
+            std::vector<int64_t> s((size_t)cnt), e((size_t)cnt);
+            std::vector<uint32_t> d((size_t)cnt), m((size_t)cnt);
+            int rc = lime_result_fill_host(res, c.data(), s.data(), e.data(), nullptr, nullptr);
+            if (rc == LIME_OK && min_sets_ == 0) rc = lime_result_depths(res, 0, cnt, d.data());
+            if (rc == LIME_OK && min_sets_ == 0) rc = lime_result_masks(res, 0, cnt, m.data());
+            if (rc != LIME_OK) return rc;
+            for (int64_t k = 0; k < cnt; ++k)
+                out.push_back({ReferenceRegion(sp.names[c[k]], s[k], e[k]), Membership{d[k], m[k]}});
+            return (int)LIME_OK;
+        });
+        return out;
+    }
+
+    // the same as text formatted on the device: chrom, start, end (and n_sets,
+    // mask in membership mode), tab-separated, one run per line
+    std::string bed() {
+        std::string out;
+        each_space([&](const detail::Space &sp, lime_result *res, int64_t) {
+            std::vector<const char *> nm;
+            for (auto &x : sp.names) nm.push_back(x.c_str());
+            int64_t len = 0;
+            int rc = lime_result_format_bed(res, nm.data(), nullptr, 0, &len);
+            if (rc != LIME_OK) return rc;
+            std::string text((size_t)len, '\0');
+            rc = lime_result_format_bed(res, nm.data(), &text[0], len, &len);
+            out += text;
+            return rc;
+        });
+        return out;
+    }
+
+   private:
+    template <class F>
+    void each_space(F &&f) {
+        const int k = (int)rdds_.size();
+        if (k < 1 || k > 32) throw Error(LIME_ERR_ARG, "multiinter takes 1 to 32 inputs");
+        if (min_sets_ < 0 || min_sets_ > k)
+            throw Error(LIME_ERR_ARG, "min_sets outside [0, number of inputs]");
+        std::map<std::string, int64_t> ext;
+        for (auto &r : rdds_)
+            for (auto &kv : r) {
+                auto &e = ext[kv.first.referenceName];
+                e = std::max(e, kv.first.end);
+            }
+        std::vector<std::string> n;
+        std::vector<int64_t> l;
+        for (auto &kv : ext) {
+            n.push_back(kv.first);
+            l.push_back(kv.second);
+        }
+        detail::Genome gn(n, l);
+        std::vector<std::vector<std::vector<size_t>>> parts;
+        for (auto &r : rdds_) parts.push_back(gn.split(r, detail::all_rows(r.size())));
+        for (size_t q = 0; q < gn.spaces.size(); ++q) {
+            const auto &sp = *gn.spaces[q];
+            std::vector<detail::SetHandle> sets((size_t)k);
+            std::vector<const lime_set *> hs;
+            for (int i = 0; i < k; ++i) {
+                detail::upload(eng_.ctx(), sp, rdds_[(size_t)i], parts[(size_t)i][q],
+                               sets[(size_t)i]);
+                hs.push_back(sets[(size_t)i].h);
+            }
+            lime_result *res = nullptr;
+            int64_t cnt = 0;
+            check(lime_multiinter(eng_.ctx(), k, hs.data(), min_sets_, &res, &cnt));
+            const int rc = f(sp, res, cnt);
+            lime_result_destroy(res);
+            check(rc);
+        }
+    }
+
+    std::vector<RDD<T>> rdds_;
+    int min_sets_;
+    Engine &eng_;
+};
+
 // What the right side does to one left row: the right rows that overlap it,
 // the bases of it they cover, and the sum of their overlaps.
 struct Annot {

@@ -104,6 +104,9 @@ SIGNATURES = {
     "lime_result_depths": (C.c_int, [vp, i64, i64, P(u32)]),
     "lime_result_depth_device": (C.c_int, [vp, pp]),
     "lime_result_depth_stats": (C.c_int, [vp, P(u64), P(u64), P(u32)]),
+    "lime_multiinter": (C.c_int, [vp, i32, P(vp), i32, pp, P(i64)]),
+    "lime_result_masks": (C.c_int, [vp, i64, i64, P(u32)]),
+    "lime_result_mask_device": (C.c_int, [vp, pp]),
     "lime_annotate": (C.c_int, [vp, vp, vp, pp]),
     "lime_annot_size": (i64, [vp]),
     "lime_annot_fill_host": (C.c_int, [vp, i64, i64, P(i64), P(u32), P(u32), P(u64)]),

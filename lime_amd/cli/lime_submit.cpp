@@ -23,6 +23,13 @@
 //                               order -- chrom, start, end, n_hits, covered,
 //                               overlap_bases, then the row's BED name field
 //                               if it has one
+//   multiinter A.bed B.bed [C.bed ...] [-min N]   no reference command (bedtools
+//                               multiinter): 1 to 32 inputs, strand ignored.
+//                               Without -min (or -min 0) the maximal runs of
+//                               constant set membership -- chrom, start, end,
+//                               n_sets, mask (decimal, bit i = the i-th input);
+//                               with -min N the regions at least N inputs cover
+//                               -- chrom, start, end.  Formatted on the device.
 //
 // Everything before "--" is accepted and ignored (there is no Spark).
 // Output is one region per line, tab-separated (chrom, start, end), followed
@@ -54,6 +61,7 @@ const Cmd kCommands[] = {
     {"closest", "Find the closest region in the second input for each region of the first"},
     {"coverage", "Compute the coverage over defined intervals"},
     {"annotate", "Count the hits, covered bases and overlap of the second input on each region of the first"},
+    {"multiinter", "Regions by the input sets that cover them (membership, or at least -min of them)"},
 };
 
 void usage() {
@@ -186,6 +194,21 @@ int run(const std::vector<std::string> &args) {
             if (!o.second.first.empty()) printf("\t%s", o.second.first.c_str());
             printf("\n");
         }
+    } else if (cmd == "multiinter") {
+        need(1);
+        int min_sets = 0;
+        std::vector<RDD<std::string>> in;
+        for (size_t i = 1; i < args.size(); ++i) {
+            if (args[i] == "-min") {
+                if (i + 1 >= args.size()) throw Error(LIME_ERR_ARG, "multiinter: -min needs a number");
+                min_sets = std::stoi(args[++i]);
+            } else {
+                if (in.size() == 32) throw Error(LIME_ERR_ARG, "multiinter: at most 32 inputs");
+                in.push_back(load_bed(args[i], false));
+            }
+        }
+        const std::string text = DistributedMultiIntersection<std::string>(std::move(in), min_sets).bed();
+        fwrite(text.data(), 1, text.size(), stdout);
     } else if (cmd == "complement") {
         need(2);
         int32_t n = 0;

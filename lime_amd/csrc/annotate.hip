@@ -280,22 +280,6 @@ __global__ __launch_bounds__(256) void k_ann_totals(const uint32_t *__restrict__
     }
 }
 
-// B read as a plain set (merge_runs breaks a stranded set's runs at strand
-// changes; the union here is strand-blind): borrows B's arrays
-struct PlainView {
-    lime_set v;
-    explicit PlainView(const lime_set *b) {
-        v.ctx = b->ctx;
-        v.n = b->n;
-        v.gs = b->gs;
-        v.ge = b->ge;
-        v.row = b->row;
-        v.n_contigs = b->n_contigs;
-        v.d_off = b->d_off;
-    }
-    ~PlainView() { v.gs = v.ge = v.row = nullptr; }
-};
-
 unsigned grid_for(int64_t n) { return std::min<unsigned>(blocks_for(n, ANB), 8192u); }
 
 }  // namespace

@@ -221,6 +221,7 @@ lime_result::~lime_result() {
     lime::release(ctx, run_of_sorted);
     lime::release(ctx, run_strand);
     lime::release(ctx, depth);
+    lime::release(ctx, mask);
 }
 
 lime_annot::~lime_annot() {
@@ -1122,6 +1123,49 @@ int lime_result_depth_stats(const lime_result *r, uint64_t *covered_bases, uint6
     return depth_stats(r->ctx, r, covered_bases, depth_bases, max_depth);
 }
 
+// -------------------------------------------------------------- multiinter
+int lime_multiinter(lime_ctx *ctx, int32_t k, const lime_set *const *sets, int32_t min_sets,
+                    lime_result **out, int64_t *n_runs) {
+    if (!ctx || !sets || !out) return fail(LIME_ERR_ARG, "bad multiinter arguments");
+    if (k < 1 || k > 32) return fail(LIME_ERR_ARG, "multiinter takes 1 to 32 sets");
+    if (min_sets < 0 || min_sets > k)
+        return fail(LIME_ERR_ARG, "min_sets outside [0, number of sets]");
+    for (int32_t i = 0; i < k; ++i) {
+        if (!sets[i]) return fail(LIME_ERR_ARG, "a set is null");
+        LIME_TRY(same_ctx(ctx, sets[i]));
+        if (!same_space(sets[0], sets[i]))
+            return fail(LIME_ERR_ARG, "sets live in different coordinate spaces");
+        if (sets[i]->min_shift) return fail(LIME_ERR_ARG, "multiinter needs fully sorted sets");
+    }
+    hipSetDevice(ctx->device);
+    std::unique_ptr<lime_result> r = new_result(ctx, sets[0]);
+    LIME_TRY(multiinter_run(ctx, k, sets, min_sets, r.get()));
+    if (n_runs) *n_runs = r->n;
+    *out = r.release();
+    return LIME_OK;
+}
+
+int lime_result_masks(const lime_result *r, int64_t first, int64_t count, uint32_t *mask) {
+    if (!r) return fail(LIME_ERR_ARG, "result is null");
+    if (!r->mask) return fail(LIME_ERR_ARG, "not a membership result");
+    if (first < 0 || count < 0 || first + count > r->n || (count > 0 && !mask))
+        return fail(LIME_ERR_ARG, "range outside the result");
+    lime_ctx *ctx = r->ctx;
+    hipSetDevice(ctx->device);
+    if (count == 0) return LIME_OK;
+    LIME_HIP(hipMemcpyAsync(mask, r->mask + first, 4 * (size_t)count, hipMemcpyDeviceToHost,
+                            S(ctx)));
+    LIME_HIP(hipStreamSynchronize(S(ctx)));
+    return LIME_OK;
+}
+
+int lime_result_mask_device(const lime_result *r, const uint32_t **mask) {
+    if (!r || !mask) return fail(LIME_ERR_ARG, "bad arguments");
+    if (!r->mask) return fail(LIME_ERR_ARG, "not a membership result");
+    *mask = r->mask;
+    return LIME_OK;
+}
+
 // ---------------------------------------------------------------- annotate
 static int names_of(const char *const *names, int32_t n, std::vector<std::string> &v);
 
@@ -1357,8 +1401,9 @@ int lime_result_format_bed(const lime_result *r, const char *const *names, char 
     std::vector<std::string> nm;
     LIME_TRY(names_of(names, r->n_contigs, nm));
     hipSetDevice(r->ctx->device);
-    // (a coverage result: its depths as the fourth column, a bedGraph)
-    return format_bed(r->ctx, r->off, nm, r->n, r->gs, r->ge, r->depth, out, cap, len);
+    // (a coverage result: its depths as the fourth column, a bedGraph; a
+    // membership result: n_sets and the mask)
+    return format_bed(r->ctx, r->off, nm, r->n, r->gs, r->ge, r->depth, out, cap, len, r->mask);
 }
 
 int lime_result_device_arrays(const lime_result *r, const uint32_t **gs, const uint32_t **ge) {

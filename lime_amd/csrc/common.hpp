@@ -162,7 +162,9 @@ struct lime_result {
     uint32_t *b_row = nullptr;  // may be null (0xffffffff = None)
     uint32_t *run_of_sorted = nullptr;  // merge only (per sorted input)
     int8_t *run_strand = nullptr;       // merge of a stranded set: strand per run
-    uint32_t *depth = nullptr;          // coverage only: depth of every run
+    uint32_t *depth = nullptr;          // coverage: depth of every run; multiinter
+                                        // membership: its number of sets
+    uint32_t *mask = nullptr;           // multiinter membership only: sets of every run
     const lime_set *src = nullptr;      // merge only
     uint32_t *d_off = nullptr;          // contig offsets used to localise
     int32_t n_contigs = 0;
@@ -312,6 +314,23 @@ class LazyScope {
     const bool had_pmax_, had_tie_;
 };
 
+// A set read as a plain one (merge_runs breaks a stranded set's runs at strand
+// changes; annotate's and multiinter's unions are strand-blind): borrows the
+// set's arrays
+struct PlainView {
+    lime_set v;
+    explicit PlainView(const lime_set *b) {
+        v.ctx = b->ctx;
+        v.n = b->n;
+        v.gs = b->gs;
+        v.ge = b->ge;
+        v.row = b->row;
+        v.n_contigs = b->n_contigs;
+        v.d_off = b->d_off;
+    }
+    ~PlainView() { v.gs = v.ge = v.row = nullptr; }
+};
+
 // read a device scalar back to the host (synchronises the context stream)
 int read_back(lime_ctx *c, void *host, const void *dev, size_t bytes);
 
@@ -350,6 +369,11 @@ int coverage_run(lime_ctx *ctx, const lime_set *set, lime_result *res);
 // sum of widths, sum of width x depth and maximum depth of a coverage result
 int depth_stats(lime_ctx *ctx, const lime_result *res, uint64_t *covered, uint64_t *depth_bases,
                 uint32_t *max_depth);
+// membership runs (min_sets == 0; res owns gs / ge / mask / depth) or the
+// regions covered by at least min_sets of the k sets (res owns gs / ge)
+// (multiinter.hip); the sets are sorted and of one space
+int multiinter_run(lime_ctx *ctx, int k, const lime_set *const *sets, int min_sets,
+                   lime_result *res);
 // a set's ends sorted ascending, as the starts of the temporary set *ends
 // (coverage.hip; the caller's, empty on entry)
 int sorted_ends(lime_ctx *ctx, const lime_set *set, lime_set *ends);

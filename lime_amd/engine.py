@@ -259,6 +259,20 @@ class Result:
         check(_lib().lime_result_depth_stats(self._h, C.byref(cov), C.byref(db), C.byref(mx)))
         return cov.value, db.value, mx.value
 
+    def masks(self, first=0, count=None):
+        """membership results (Context.multiinter, min_sets = 0): masks of runs
+        [first, first + count) (u32, bit i = the i-th set passed)"""
+        count = self.n - first if count is None else int(count)
+        out = np.zeros(max(count, 1), dtype=np.uint32)
+        check(_lib().lime_result_masks(self._h, int(first), count, _ptr(out, u32)))
+        return out[:count]
+
+    def mask_device(self):
+        """membership results: device pointer of the runs' masks (u32)"""
+        d = vp()
+        check(_lib().lime_result_mask_device(self._h, C.byref(d)))
+        return d.value
+
     def copy_range(self, first, count):
         """host copy of regions [first, first+count) in GLOBAL coordinates"""
         gs = np.zeros(count, dtype=np.uint32)
@@ -577,6 +591,19 @@ class Context:
         h, n = vp(), i64()
         check(_lib().lime_coverage(self._h, a._h, C.byref(h), C.byref(n)))
         return Result(self, h, a.space)
+
+    def multiinter(self, sets, min_sets=0):
+        """1 to 32 sets of one space at once.  min_sets = 0: the maximal runs
+        of constant non-zero set membership (Result.masks, bit i = sets[i];
+        Result.depths gives n_sets, depth_stats its totals; to_bed five
+        columns).  1 <= min_sets <= len(sets): the regions covered by at least
+        that many of the sets (a plain Result)."""
+        sets = list(sets)
+        k = len(sets)
+        hs = (vp * max(k, 1))(*[s._h for s in sets])
+        h, n = vp(), i64()
+        check(_lib().lime_multiinter(self._h, k, hs, int(min_sets), C.byref(h), C.byref(n)))
+        return Result(self, h, sets[0].space, keep=tuple(sets))
 
     def annotate(self, a, b):
         """per row of a: the rows of b that hit it, the bases of it they

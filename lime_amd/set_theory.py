@@ -23,6 +23,10 @@ lime-core/src/main/scala/org/bdgenomics/lime/set_theory/:
     DistributedCoverage(rddToCompute, partitionMap).compute()
         -> [(ReferenceRegion, depth)]              (no lime-core class: the
                                                     CLI stub cli/Coverage.scala)
+    DistributedMultiIntersection([rdd, ...], min_sets=0).compute()
+        -> [(ReferenceRegion, (n_sets, mask))]     (no lime-core class: the
+           or [ReferenceRegion] for min_sets >= 1   membership of 1 to 32 inputs,
+                                                    or their m-of-k consensus)
     DistributedAnnotate(leftRdd, rightRdd, partitionMap).compute()
         -> [(leftRegion, (T, n_hits, covered, overlap_bases))]
                                                    (no lime-core class: every
@@ -426,6 +430,50 @@ class DistributedCoverage(_Op):
             A.close()
             out += [(ReferenceRegion(space.names[h["contig"][k]], int(h["start"][k]),
                                      int(h["end"][k])), int(d[k])) for k in range(len(d))]
+        return out
+
+
+class DistributedMultiIntersection(_Op):
+    """1 to 32 inputs at once (bedtools multiinter).  min_sets = 0:
+    [(ReferenceRegion, (n_sets, mask))] for every maximal interval of one
+    contig on which the set of inputs covering a base is constant and not
+    empty (bit i of mask = rdds[i]).  1 <= min_sets <= len(rdds):
+    [ReferenceRegion], the maximal intervals covered by at least min_sets of
+    the inputs (1: the union of everything, len(rdds): the k-way AND).
+    Contigs in RegionOrdering.  NOT a lime-core class; the name follows the
+    mirror's Distributed* family.  Strand is ignored and the regions are
+    unstranded; zero-width rows add nothing.  Contig-local, so a genome cut
+    into several spaces runs one space after the other."""
+
+    def __init__(self, rdds, min_sets=0, ctx=None):
+        super().__init__(ctx)
+        self.rdds = [list(r) for r in rdds]
+        self.min_sets = int(min_sets)
+
+    def compute(self):
+        k, m = len(self.rdds), self.min_sets
+        if not 1 <= k <= 32:
+            raise _ffi.LimeError(1, "multiinter takes 1 to 32 inputs")  # LIME_ERR_ARG
+        if not 0 <= m <= k:
+            raise _ffi.LimeError(1, "min_sets outside [0, number of inputs]")
+        regs = [_rows(r)[0] for r in self.rdds]
+        genome = _space_for(*regs)
+        parts = [genome.split(rg, range(len(rg))) for rg in regs]
+        out = []
+        for q, space in enumerate(genome.spaces):
+            if not any(p[q] for p in parts):
+                continue
+            sets = [self.ctx.set_from_host(space, *_arrays(space, rg, p[q]))
+                    for rg, p in zip(regs, parts)]
+            res = self.ctx.multiinter(sets, m)
+            h = res.to_host()
+            info = zip(res.depths().tolist(), res.masks().tolist()) if m == 0 else None
+            res.close()
+            for s in sets:
+                s.close()
+            rr = [ReferenceRegion(space.names[h["contig"][j]], int(h["start"][j]),
+                                  int(h["end"][j])) for j in range(len(h["start"]))]
+            out += list(zip(rr, info)) if m == 0 else rr
         return out
 
 

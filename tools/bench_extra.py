@@ -41,6 +41,16 @@ the 8(f) rows (bench.py measures the headline config C2).  Single GPU; one JSON 
       region), the intersect count pass on the same sets beside it, and the
       identity sum(n_hits) == the plan's pair count
 
+  multiinter  membership runs and m-of-8 consensus (lime_multiinter) of C5's 8
+      sets (8 x 1.25e8 rows, len U[10,40], seeds 0x50..0x57; built and sorted
+      outside the timed region): membership mode, min_sets = 5 and min_sets =
+      8, each timed by device events; beside them the sort of the events alone
+      (as many zero-width global rows as the call sorts) and C5's own path
+      (bitset_and_from_device + its runs from the unsorted rows), the only
+      answer the bit-per-base path has to any of these.  Identities: min_sets
+      = 8 against the C5 runs (count and covered bases), and the membership
+      depth_bases against the sum of the sets' bitset popcounts
+
 Inputs are generated on the device (counter-based RNG) outside the timed
 region; every step starts from unsorted rows in HBM.
 """
@@ -60,7 +70,8 @@ def main():
     p = argparse.ArgumentParser()
     p.add_argument("--workload", required=True,
                    choices=["c3", "c4", "c5", "bed", "closest", "closest_single", "window",
-                            "subtract", "b1_merge", "b1_pair", "coverage", "annotate"])
+                            "subtract", "b1_merge", "b1_pair", "coverage", "annotate",
+                            "multiinter"])
     p.add_argument("--input", choices=["pileup", "uniform"], default="pileup",
                    help="coverage: C3's pile-up rows or uniform rows as C2's")
     p.add_argument("--steps", type=int, default=3)
@@ -215,6 +226,83 @@ def main():
                     "pairs_equals_intersect_count": pairs == n_pairs, "runs_of_b": nr}, \
                 {"kernel": "lime_annotate (sort of ends, scans, merge, k_ann_split, k_annotate)",
                  "bound": "hbm", "achieved": b / (ms * 1e-3) / 1e9, "alg_bytes": b}
+    elif a.workload == "multiinter":
+        k = 8
+        per = int(1.25e8 * a.scale)
+        ins = [gen(per, 0x50 + i, 10, 40) for i in range(k)]
+        sets = [mkset(x) for x in ins]  # (sorted outside the timed region)
+        pops = []
+        for x in sets:  # the bases of every set, one bitset at a time
+            b = ctx.bitset(x)
+            pops.append(b.popcount())
+            b.close()
+        n = k * per
+        # as many events as the call sorts: both ends of every set's merge runs
+        n_ev = 0
+        for x in sets:
+            m = ctx.merge(x)
+            n_ev += 2 * m.n
+            m.close()
+        ev_keys = torch.empty(max(n_ev, 1), dtype=torch.int32, device=dev)
+        tmp = [torch.empty(per, dtype=torch.int32, device=dev) for _ in range(2)]
+        at = 0
+        for x in sets:  # (any keys of the right count and range: the sets' starts)
+            take = min(x.n, n_ev - at)
+            x.copy_rows_device(0, take, ev_keys[at:].data_ptr(), tmp[0].data_ptr(),
+                               tmp[1].data_ptr())
+            at += take
+        ctx.synchronize()
+        del tmp
+        while at < n_ev:  # fewer rows than events: repeat what is there
+            take = min(at, n_ev - at)
+            ev_keys[at:at + take].copy_(ev_keys[:take])
+            at += take
+        ev_rows = torch.zeros(n_ev, dtype=torch.int32, device=dev)
+
+        def step(rec):
+            t0 = ev()
+            r0 = ctx.multiinter(sets, 0)
+            t1 = ev()
+            r5 = ctx.multiinter(sets, 5)
+            t2 = ev()
+            r8 = ctx.multiinter(sets, 8)
+            t3 = ev()
+            E = ctx.set_from_global(space, n_ev, ev_keys.data_ptr(), ev_keys.data_ptr(),
+                                    ev_rows.data_ptr())
+            t4 = ev()
+            fused = ctx.bitset_and_from_device(
+                space, [(x[0], x[1].data_ptr(), x[2].data_ptr(), x[3].data_ptr()) for x in ins])
+            c5 = ctx.bitset_runs(0, fused)
+            t5 = ev()
+            h8 = r8.copy_range(0, r8.n) if r8.n else (None, None)
+            cov8 = int((h8[1].astype("int64") - h8[0].astype("int64")).sum()) if r8.n else 0
+            rec.append((t0, t1, t2, t3, t4, t5, r0.n, r5.n, r8.n, c5.n, r0.depth_stats(), cov8,
+                        fused.popcount()))
+            for h in (c5, fused, E, r8, r5, r0):
+                h.close()
+        units, unit = n, "intervals/s"
+        desc = f"multiinter: membership runs of {k} x {per} sorted rows (C5's sets, len U[10,40])"
+
+        def step_ms(recs):  # the rate is the membership call's
+            return sum(r[0].elapsed_time(r[1]) for r in recs) / len(recs)
+
+        def roof(rec):
+            t0, t1, t2, t3, t4, t5, n0, n5, n8, nc5, (cov, db, mx), cov8, pop8 = rec[-1]
+            ms, sort_ms = t0.elapsed_time(t1), t3.elapsed_time(t4)
+            # the walks: k_mi_tile_xor (4) + k_mi twice (8 + 8) per event, 16 per run
+            b = 20 * n_ev + 16 * n0
+            walk = max(ms - sort_ms, 1e-6)
+            return {"membership_ms": ms, "min_sets_5_ms": t1.elapsed_time(t2),
+                    "min_sets_8_ms": t2.elapsed_time(t3), "sort_of_events_ms": sort_ms,
+                    "sort_share": sort_ms / ms, "c5_bitset_and_runs_ms": t4.elapsed_time(t5),
+                    "events": n_ev, "runs_membership": n0, "runs_min_sets_5": n5,
+                    "runs_min_sets_8": n8, "runs_c5": nc5,
+                    "depth_stats": {"covered_bases": cov, "depth_bases": db, "max_depth": mx},
+                    "min_sets_8_equals_c5": n8 == nc5 and cov8 == pop8,
+                    "depth_bases_equals_sum_of_popcounts": db == sum(pops)}, \
+                {"kernel": "merges, event writes, k_mi_tile_xor + k_mi count + fill (all but "
+                           "the sort of the events)",
+                 "bound": "hbm", "achieved": b / (walk * 1e-3) / 1e9, "alg_bytes": b}
     elif a.workload == "b1_merge":
         inp = gen(int(1e9 * a.scale), 0x1B, 150, 600, pile=(4_000_000, 150))
         n = inp[0]
