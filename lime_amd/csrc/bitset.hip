@@ -25,7 +25,7 @@ constexpr int BB = 256;
 constexpr int BW = 16;            // words per thread
 constexpr int BT = BB * BW;       // words per tile
 constexpr int MAXK = 16;
-constexpr int MAXPAD = 64;        // contig pads per tile handled in LDS
+constexpr int MAXPAD = 64;        // contig pads of a tile staged in LDS at a time (a batch)
 
 __global__ __launch_bounds__(BB) void k_paint(const uint32_t *__restrict__ rgs,
                                               const uint32_t *__restrict__ rge, int64_t nr,
@@ -987,6 +987,23 @@ __device__ __forceinline__ uint64_t not_mask(const OpArgs &a, int64_t w, uint64_
     return x;
 }
 
+// a further batch of pads (s_pad[0 .. npad)) cleared from the words x[0 .. N)
+// that start at bit b0: one pad at a time and not unrolled -- only tiles with
+// more than MAXPAD pads come here, and the common path must not pay for it
+// in registers
+template <int N>
+__device__ __forceinline__ void clear_pads(uint64_t (&x)[N], int64_t b0, const uint32_t *s_pad,
+                                           int npad) {
+#pragma unroll 1
+    for (int p = 0; p < npad; ++p) {
+        const int64_t d = (int64_t)s_pad[p] - b0;
+        if (d < 0 || d >= 64 * N) continue;
+#pragma unroll
+        for (int k = 0; k < N; ++k)
+            if ((int)(d >> 6) == k) x[k] &= ~(1ull << (d & 63));
+    }
+}
+
 // word pairs (w, w + 1), w = w0 + 2 (t + j BB): 16-B loads, all issued
 // before any is used (0 past the window)
 // Tile images in LDS hold word q of [w0 - 1, w0 + TW) at ipad(q): one pad
@@ -1024,14 +1041,20 @@ template <int NT = BB, int TW = BT>
 __device__ __forceinline__ void stage_tile(const OpArgs &a, int64_t w0, unsigned long long *img,
                                            uint32_t *s_pad, int *s_npad) {
     constexpr int SJ = TW / (2 * NT);
-    if (a.op == 1 && threadIdx.x == 0) {
-        const int64_t lo = (a.word0 + (w0 > 0 ? w0 - 1 : 0)) * 64, hi = (a.word0 + w0 + TW) * 64;
-        // first contig whose pad bit off[c + 1] - 1 is >= lo
-        int64_t c = dev::lower_bound(a.off + 1, 0, (int64_t)a.nc, (uint64_t)lo + 1);
+    // the tile's pads from contig pc on, MAXPAD at a time (thread 0)
+    int64_t pc = 0;
+    auto stage_pads = [&]() {
+        const int64_t hi = (a.word0 + w0 + TW) * 64;
         int np = 0;
-        for (; c < a.nc && (int64_t)a.off[c + 1] - 1 < hi && np < MAXPAD; ++c)
-            s_pad[np++] = a.off[c + 1] - 1;
+        for (; pc < a.nc && (int64_t)a.off[pc + 1] - 1 < hi && np < MAXPAD; ++pc)
+            s_pad[np++] = a.off[pc + 1] - 1;
         *s_npad = np;
+    };
+    if (a.op == 1 && threadIdx.x == 0) {
+        const int64_t lo = (a.word0 + (w0 > 0 ? w0 - 1 : 0)) * 64;
+        // first contig whose pad bit off[c + 1] - 1 is >= lo
+        pc = dev::lower_bound(a.off + 1, 0, (int64_t)a.nc, (uint64_t)lo + 1);
+        stage_pads();
     }
     const int64_t nw = a.n_words;
     uint64_t x0[SJ], x1[SJ];
@@ -1059,6 +1082,29 @@ __device__ __forceinline__ void stage_tile(const OpArgs &a, int64_t w0, unsigned
             x1[j] = w + 1 < nw ? not_mask(a, w + 1, ~x1[j], s_pad, npad) : 0ull;
         }
         if (threadIdx.x == 0 && w0 > 0 && w0 - 1 < nw) xb = not_mask(a, w0 - 1, xb, s_pad, npad);
+        // a full batch: the tile may hold more pads (contigs under ~4 kb),
+        // cleared batch by batch (*s_npad: a block-uniform loop)
+        for (int more = npad; more == MAXPAD;) {
+            __syncthreads();  // (every thread is done with the batch staged)
+            if (threadIdx.x == 0) stage_pads();
+            __syncthreads();
+            more = *s_npad;
+#pragma unroll 1
+            for (int p = 0; p < more; ++p) {  // (words past the window are 0 and stay so)
+                const int64_t d0 = (int64_t)s_pad[p] - (a.word0 + w0 + 2 * threadIdx.x) * 64;
+#pragma unroll
+                for (int j = 0; j < SJ; ++j) {
+                    const int64_t d = d0 - (int64_t)j * NT * 128;
+                    if (d >= 0 && d < 64) x0[j] &= ~(1ull << d);
+                    if (d >= 64 && d < 128) x1[j] &= ~(1ull << (d - 64));
+                }
+            }
+            if (threadIdx.x == 0 && w0 > 0 && w0 - 1 < nw) {
+                uint64_t b[1] = {xb};
+                clear_pads(b, (a.word0 + w0 - 1) * 64, s_pad, more);
+                xb = b[0];
+            }
+        }
     }
 #pragma unroll
     for (int j = 0; j < SJ; ++j) {
@@ -1181,17 +1227,25 @@ __global__ __launch_bounds__(EV_NT) void k_ev_local(OpArgs a, uint32_t *__restri
     const int64_t nw = a.n_words;
     const int w = threadIdx.x / 64, lane = dev::lane_id();
     const int64_t q0 = w0 + (int64_t)threadIdx.x * EV_W;  // the thread's first word
-    if (a.op == 1 && w == 0) {  // NOT: the contig pads of the tile, by wave 0
-        // (a 65-ary search, then lane l tests the l-th pad from there: the
-        // serial binary search by one lane cost C4's complement ~15 us)
-        const int64_t lo = (a.word0 + (w0 > 0 ? w0 - 1 : 0)) * 64, hi = (a.word0 + w0 + EV_TW) * 64;
+    // NOT: the contig pads of the tile, MAXPAD at a time by wave 0: lane l
+    // tests the l-th pad from contig c
+    const int64_t phi = (a.word0 + w0 + EV_TW) * 64;
+    auto stage_pads = [&](int64_t c) {
         static_assert(MAXPAD == 64, "one pad per lane");
-        const int64_t c = dev::wave_lower_bound(a.off + 1, (int64_t)a.nc, lo + 1) + lane;
+        c += lane;
         const int64_t pad = c < a.nc ? (int64_t)a.off[c + 1] - 1 : INT64_MAX;
-        const bool in = pad < hi;  // (pads ascend: a prefix of the lanes)
+        const bool in = pad < phi;  // (pads ascend: a prefix of the lanes)
         const uint64_t m = __ballot(in);
         if (in) s_pad[lane] = (uint32_t)pad;
         if (lane == 0) s_npad = __popcll(m);
+    };
+    int64_t pc = 0;  // (wave 0) the contig of the tile's first pad
+    if (a.op == 1 && w == 0) {
+        // (a 65-ary search: the serial binary search by one lane cost C4's
+        // complement ~15 us)
+        const int64_t lo = (a.word0 + (w0 > 0 ? w0 - 1 : 0)) * 64;
+        pc = dev::wave_lower_bound(a.off + 1, (int64_t)a.nc, lo + 1);
+        stage_pads(pc);
     }
     uint64_t x[EV_W];
     const int nops = a.op == 4 ? a.k : (a.op >= 2 ? 2 : 1);
@@ -1228,6 +1282,20 @@ __global__ __launch_bounds__(EV_NT) void k_ev_local(OpArgs a, uint32_t *__restri
         for (int k = 0; k < EV_W; ++k)
             x[k] = q0 + k < nw ? not_mask(a, q0 + k, ~x[k], s_pad, npad) : 0ull;
         if (threadIdx.x == 0 && w0 > 0 && w0 - 1 < nw) xb = not_mask(a, w0 - 1, xb, s_pad, npad);
+        // a full batch: the tile may hold more pads (contigs under ~2 kb),
+        // cleared batch by batch (s_npad: a block-uniform loop)
+        for (int more = npad; more == MAXPAD;) {
+            __syncthreads();  // (every thread is done with the batch staged)
+            if (w == 0) stage_pads(pc += MAXPAD);
+            __syncthreads();
+            more = s_npad;
+            clear_pads(x, (a.word0 + q0) * 64, s_pad, more);  // (words past the window stay 0)
+            if (threadIdx.x == 0 && w0 > 0 && w0 - 1 < nw) {
+                uint64_t b[1] = {xb};
+                clear_pads(b, (a.word0 + w0 - 1) * 64, s_pad, more);
+                xb = b[0];
+            }
+        }
     }
     // left neighbour of the thread's first word
     if (lane == 63) s_last[w] = x[EV_W - 1];
@@ -2005,6 +2073,13 @@ int bitset_runs(lime_ctx *ctx, int op, int k, const lime_bitset *const *sets, li
     // binned operands (bitsets from rows): the runs straight from the bins,
     // unless a tile overflows its event slot; else (or then) from words
     const int nin = op == 4 ? k : (op >= 2 ? 2 : 1);
+    // LIME_TRACE_RUNS: one line per call naming the path taken (read per
+    // call: tests set it at run time)
+    const bool trace = getenv("LIME_TRACE_RUNS") != nullptr;
+    const char *first = "";  // ("fused overflow, " once the fused path gave up)
+    auto took = [&](const char *path) {
+        if (trace) fprintf(stderr, "lime: bitset_runs op=%d k=%d %s%s\n", op, k, first, path);
+    };
     // (a complemented operand must be ONE binned set: ~(x & y) is not a
     // complement per set; at most MAXK binned sets in all)
     bool binned = a->n_words > 0;
@@ -2019,7 +2094,11 @@ int bitset_runs(lime_ctx *ctx, int op, int k, const lime_bitset *const *sets, li
     if (binned) {
         bool overflow = false;
         LIME_TRY(runs_binned(ctx, op, nin, sets, res, &overflow));
-        if (!overflow) return LIME_OK;
+        if (!overflow) {
+            took("fused");
+            return LIME_OK;
+        }
+        first = "fused overflow, ";
     }
     PaintScope painted(nin, sets);
     for (int i = 0; i < nin; ++i) LIME_TRY(bitset_paint(ctx, sets[i]));
@@ -2061,6 +2140,7 @@ int bitset_runs(lime_ctx *ctx, int op, int k, const lime_bitset *const *sets, li
     // closes there (a shard window may end on any word)
     const int64_t nt = a->n_words == 0 ? 0 : a->n_words / BT + 1;
     if (nt == 0) {  // an empty window (e.g. a zero-width shard): no runs
+        took("empty window");
         LIME_TRY(alloc(ctx, &res->gs, 1));
         LIME_TRY(alloc(ctx, &res->ge, 1));
         res->n = 0;
@@ -2103,6 +2183,7 @@ int bitset_runs(lime_ctx *ctx, int op, int k, const lime_bitset *const *sets, li
         unsigned int h[2] = {0, 0};
         LIME_TRY(read_back(ctx, h, hdr, sizeof(h)));
         if (!h[0]) {
+            took("words one-pass");
             if (h[1] & 1u) return fail(LIME_ERR_DEVICE, "bitset run extraction: odd event count");
             const int64_t nr = h[1] / 2;
             if (cap >= 0) {
@@ -2129,6 +2210,7 @@ int bitset_runs(lime_ctx *ctx, int op, int k, const lime_bitset *const *sets, li
             release(ctx, res->ge);
         }
     }
+    took("words two-pass");
     PoolPtr<uint32_t> tcnt, toff, total;
     LIME_TRY(tcnt.alloc(ctx, (size_t)nt));
     LIME_TRY(toff.alloc(ctx, (size_t)nt));
