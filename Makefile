@@ -72,6 +72,7 @@ build/var3/liblime_amd.so: $(HIP_SRCS) $(SRC)/common.hpp include/lime_amd.h $(CP
 
 # tuning variants of one translation unit (tools/gpu_ab.sh A/B only):
 #   make build/var_<name>/liblime_amd.so VAR_SRC=merge VAR_DEFS="-DLIME_MS2_NT=256"
+#   make build/var_nopack/liblime_amd.so VAR_SRC=intersect VAR_DEFS="-DLIME_FILL_PACK=0"
 build/var_%/liblime_amd.so: $(HIP_SRCS) $(SRC)/common.hpp include/lime_amd.h $(CPP_OBJS) $(HIP_OBJS)
 	@mkdir -p build/var_$*
 	$(HIPCC) $(HIPFLAGS) $(VAR_DEFS) -c $(SRC)/$(VAR_SRC).hip -o build/var_$*/$(VAR_SRC).o

@@ -54,6 +54,7 @@ struct PairsPlan {
         release(ctx, toff);
         release(ctx, win);
         release(ctx, tseg);
+        release(ctx, tpk);
     }
     lime_ctx *ctx;
     const lime_set *A, *B;
@@ -66,6 +67,7 @@ struct PairsPlan {
     uint64_t *toff = nullptr;                  // per tile exclusive offsets
     uint32_t *win = nullptr;                   // per tile partner window [lo, hi)
     uint32_t *tseg = nullptr;                  // per tile contig offset (0xffffffff: mixed)
+    uint32_t *tpk = nullptr;                   // per tile (packed form?, first owner start g0)
     int64_t total = 0;
     int tpf = 1;  // owner tiles per fill commit (k_fill<TPF>)
     // window plans (DistributedWindow): A is the widened set W, A_out the
@@ -83,6 +85,22 @@ constexpr int OPT = 4;               // owners per thread
 constexpr int OT = IB * OPT;         // owners per tile
 constexpr int WCAP = 4096;           // LDS window capacity (partner starts)
 constexpr int64_t SBLK = 131072;     // output records per fill workgroup
+
+// Packed owner words between k_count<false, true> and k_fill: a tile whose
+// partner window, pair total, owner starts and owner widths all fit hands
+// the fill its owners' (lo, off, gs, ge) in the 8 bytes per owner that
+// otherwise hold (lo, off) alone,
+//   olo[]  = (lo - wlo) << PK_OFF_BITS | off     wlo: the tile's window start
+//   ocnt[] = (gs - g0) << PK_W_BITS | (ge - gs)  g0: the tile's first owner start
+// so the fill reads 12 B per owner (two words and the row) instead of 20.
+// tpk[2 t] says which form tile t has, tpk[2 t + 1] is its g0.
+#ifndef LIME_FILL_PACK
+#define LIME_FILL_PACK 1  // 0: every tile keeps the plain (lo, off) words
+#endif
+constexpr int PK_WIN = 2048;     // longest window of a packed tile (lo - wlo <= PK_WIN)
+constexpr int PK_OFF_BITS = 20;  // tile-local offsets (and the tile's total) below 2^20
+constexpr int PK_W_BITS = 16;    // ge - gs and gs - g0 below 2^16
+static_assert(PK_WIN < (1 << (32 - PK_OFF_BITS)), "lo - wlo must fit above the offset bits");
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
@@ -234,16 +252,23 @@ __global__ __launch_bounds__(256) void k_windows_lane(StreamArgs sa, int64_t tp,
 // offset within the tile (OFFS = true, what the fill stages: no scan left in
 // the fill's per-tile critical path).  Thread t handles the OPT consecutive
 // owners 4t .. 4t+3 of the tile, so one block scan orders them.
+// tpk / pack: the fill's per-tile form table and whether this plan may pack
+// (OFFS only, see PK_WIN above); the packed words take the place of (lo, off)
+// in the same two stores.
 template <bool FILTER, bool OFFS>
 __global__ __launch_bounds__(IB) void k_count(StreamArgs sa, int64_t tp, int64_t threshold,
                                               const uint32_t *__restrict__ win,
                                               uint32_t *__restrict__ olo,
                                               uint32_t *__restrict__ ocnt,
                                               uint64_t *__restrict__ tcnt,
-                                              uint32_t *__restrict__ oflow) {
+                                              uint32_t *__restrict__ oflow,
+                                              uint32_t *__restrict__ tpk, int pack) {
     __shared__ uint32_t wgs[WCAP];
     __shared__ uint64_t red[IB / 64];
     __shared__ uint32_t scratch[IB / 64 + 1];
+    __shared__ uint32_t s_wide;  // an owner of the tile does not fit the packed words
+    __shared__ uint32_t s_g0;    // the tile's first owner start
+    constexpr bool PACK = OFFS && LIME_FILL_PACK != 0;
     const int64_t t = blockIdx.x;
     const int64_t o0 = t * OT;
     const int64_t o1 = min(o0 + OT, sa.no);
@@ -276,12 +301,17 @@ __global__ __launch_bounds__(IB) void k_count(StreamArgs sa, int64_t tp, int64_t
             oev[k] = j < o1 ? sa.oge[j] : 0u;
         }
     }
+    if (PACK && threadIdx.x == 0) {  // (both ordered by the barrier below)
+        s_wide = 0u;
+        s_g0 = ogv[0];
+    }
     if (in_lds && wlen > 0) {
 #pragma unroll
         for (int k = 0; k < WPT; ++k)
             if (k * IB + (int)threadIdx.x < wlen) wgs[k * IB + threadIdx.x] = wv[k];
     }
     __syncthreads();
+    const uint32_t g0 = PACK ? s_g0 : 0u;
     // lo = lb(P, o.gs + lo_off) always (subtract's spanning walk starts
     // below it); hi = lb(P, o.ge - tp + 1), the range [lo, hi) being empty
     // when hk <= lk.  In the LDS window all 2 * OPT searches of a thread run
@@ -341,19 +371,31 @@ __global__ __launch_bounds__(IB) void k_count(StreamArgs sa, int64_t tp, int64_t
     // tile-local offsets are u32 (the fill stages them as such): a tile with
     // 2^32 or more pairs is flagged below and the plan fails with
     // LIME_ERR_OVERFLOW instead of wrapping
-    uint32_t run = 0;
-    if (OFFS) {
-        uint32_t tot;
-        run = dev::block_exclusive_sum<IB>((uint32_t)csum, scratch, &tot);
+    uint32_t run = 0, tot = 0;
+    if (PACK) {
+        // each of the 256 threads below 2^20 pairs: the u32 total cannot wrap
+        bool wide = csum >= (1ull << PK_OFF_BITS);
+#pragma unroll
+        for (int k = 0; k < OPT; ++k) {
+            if (o0 + threadIdx.x * OPT + k >= o1) continue;
+            wide |= (uint32_t)(ogv[k] - g0) >= (1u << PK_W_BITS) ||
+                    (uint32_t)(oev[k] - ogv[k]) >= (1u << PK_W_BITS);
+        }
+        if (__ballot(wide) != 0 && dev::lane_id() == 0) atomicOr(&s_wide, 1u);
     }
+    if (OFFS) run = dev::block_exclusive_sum<IB>((uint32_t)csum, scratch, &tot);
     // blocked -> lane-consecutive through LDS (the window image is dead
     // now), so the olo / ocnt stores are coalesced whatever owner0's alignment
     __syncthreads();
+    const bool pk = PACK && pack && tpk && wlen <= PK_WIN && tot < (1u << PK_OFF_BITS) &&
+                    s_wide == 0u;  // (uniform)
     uint32_t *slo = wgs, *sct = wgs + OT;
 #pragma unroll
     for (int k = 0; k < OPT; ++k) {
-        slo[threadIdx.x * OPT + k] = (uint32_t)lov[k];
-        sct[threadIdx.x * OPT + k] = OFFS ? run : cv[k];
+        const uint32_t lo = (uint32_t)lov[k];
+        const uint32_t c = OFFS ? run : cv[k];
+        slo[threadIdx.x * OPT + k] = pk ? (lo - wlo) << PK_OFF_BITS | run : lo;
+        sct[threadIdx.x * OPT + k] = pk ? (ogv[k] - g0) << PK_W_BITS | (oev[k] - ogv[k]) : c;
         run += cv[k];
     }
     __syncthreads();
@@ -373,6 +415,10 @@ __global__ __launch_bounds__(IB) void k_count(StreamArgs sa, int64_t tp, int64_t
         uint64_t s = 0;
         for (int i = 0; i < IB / 64; ++i) s += red[i];
         tcnt[sa.tile0 + t] = s;
+        if (OFFS && tpk) {
+            tpk[2 * (sa.tile0 + t)] = pk ? 1u : 0u;
+            tpk[2 * (sa.tile0 + t) + 1] = g0;
+        }
         // bit 0: a tile's u32 offsets would wrap; bit 1: two adjacent tiles'
         // might (the fill then keeps one tile per commit, see k_fill)
         if (s > 0xffffffffull && oflow)
@@ -389,6 +435,7 @@ struct FillArgs {
     const uint64_t *toff;
     const uint32_t *win;   // per tile partner window [lo, hi)
     const uint32_t *tseg;  // per tile contig offset, 0xffffffff if mixed
+    const uint32_t *tpk;   // per tile (packed owner words?, g0)
     int64_t ntiles;
     int64_t total;         // pairs of the plan
     const uint32_t *off;
@@ -467,9 +514,15 @@ __device__ __forceinline__ int64_t wave_tile_of(const uint64_t *__restrict__ a, 
 // once per tile).
 template <int TPF> struct TileRegs {
     static constexpr int FO = FillShape<TPF>::FOPT, PP = FillShape<TPF>::PPT;
-    uint32_t off[FO], lo[FO], og[FO], oe[FO], orw[FO];
+    // w0 / w1: the owner's olo[] / ocnt[] words as k_count left them, (lo, off)
+    // or packed; they are taken apart at the commit, not here, so that the
+    // loads stay in flight behind the stores.  og / oe: plain tiles only
+    uint32_t w0[FO], w1[FO], og[FO], oe[FO], orw[FO];
     uint32_t pg[PP], pe[PP], pr[PP];
     uint32_t wlo, whi, seg;
+    // of this thread's own tile t + u (wave-uniform): packed form, first owner
+    // start, window start, offset within the commit
+    uint32_t pk, g0, wown, add;
     uint64_t tnext;  // toff[t1] (or the plan total): the commit's end
     int64_t t1;      // one past the commit's last owner tile
 };
@@ -485,7 +538,7 @@ __device__ __forceinline__ int tile_stream(const FillArgs &fa, int64_t t) {
 template <int TPF>
 __device__ __forceinline__ void tile_load(const FillArgs &fa, int64_t t, TileRegs<TPF> &r,
                                           const uint64_t *toff, const uint32_t *win,
-                                          const uint32_t *tseg) {
+                                          const uint32_t *tseg, const uint32_t *tpk) {
     constexpr int FO = FillShape<TPF>::FOPT, PP = FillShape<TPF>::PPT;
     // (t is wave-uniform: the stream's arguments are selected, not indexed,
     // so they stay scalar kernel-argument loads -- an indexed fa.s[st] was
@@ -498,21 +551,33 @@ __device__ __forceinline__ void tile_load(const FillArgs &fa, int64_t t, TileReg
     const int nown = (int)min((int64_t)FillShape<TPF>::OTF, sa.no - o0);
     // k_count's offsets are local to each owner tile: a thread's owners all
     // lie in tile t + u, whose offset within the commit is toff[t+u] - toff[t]
-    uint32_t add = 0;
+    // (the commit adds it, after taking a packed tile's words apart)
+    r.add = 0;
+    int64_t tu = t;  // the tile of this thread's owners
     if (TPF > 1) {
         const int u = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / (FB / TPF)));
-        if (u > 0 && t + u < t1) add = (uint32_t)(toff[t + u] - toff[t]);
+        if (u > 0 && t + u < t1) {
+            tu = t + u;
+            r.add = (uint32_t)(toff[tu] - toff[t]);
+        }
     }
+    // the tile's form, at a wave-uniform index like the tables below: a
+    // packed tile's owners are two words and the row, a plain tile's (lo, off)
+    // and the owner's start and end
+    r.pk = LIME_FILL_PACK ? tpk[2 * tu] : 0u;
+    r.g0 = LIME_FILL_PACK ? tpk[2 * tu + 1] : 0u;
+    r.wown = win[2 * tu];  // its own window start, not the commit's union
 #pragma unroll
     for (int k = 0; k < FO; ++k) {
         const int q = threadIdx.x * FO + k;
         const bool v = q < nown;
         const int64_t j = o0 + q;
-        r.off[k] = v ? fa.ocnt[sa.owner0 + j] + add : 0u;  // tile-local offsets (k_count<_, true>)
-        r.lo[k] = v ? fa.olo[sa.owner0 + j] : 0u;
-        r.og[k] = v ? sa.ogs_o[j] : 0u;
-        r.oe[k] = v ? sa.oge_o[j] : 0u;
+        r.w1[k] = v ? fa.ocnt[sa.owner0 + j] : 0u;  // tile-local offsets (k_count<_, true>)
+        r.w0[k] = v ? fa.olo[sa.owner0 + j] : 0u;
         r.orw[k] = v ? sa.orow[j] : 0u;
+        const bool pv = v && !r.pk;  // (r.pk: uniform)
+        r.og[k] = pv ? sa.ogs_o[j] : 0u;
+        r.oe[k] = pv ? sa.oge_o[j] : 0u;
     }
     r.wlo = win[2 * t];
     r.whi = win[2 * t + 1];
@@ -677,14 +742,15 @@ __device__ __forceinline__ void emit_sparse(const FillArgs &fa, const StreamArgs
 // (a few pairs per owner, ~4k records per tile) commit two tiles at a time
 // (TPF = 2) to halve that cost per record.
 template <int TPF, bool CKSUM, bool WIN>
-// toff / win / tseg: fa's per-tile tables again, as restrict arguments: read
+// toff / win / tseg / tpk: fa's per-tile tables again, as restrict arguments: read
 // at wave-uniform indices they are scalar loads (lgkmcnt), so the commit's
 // table reads never wait on the vector memory counter -- which would drain
 // the previous commit's stores first
 __global__ __launch_bounds__(FB, 2 * LIME_FILL_WGS) void k_fill(FillArgs fa, int64_t per, int64_t gran,
                                                                const uint64_t *__restrict__ toff,
                                                                const uint32_t *__restrict__ win,
-                                                               const uint32_t *__restrict__ tseg) {
+                                                               const uint32_t *__restrict__ tseg,
+                                                               const uint32_t *__restrict__ tpk) {
     constexpr int OTF = FillShape<TPF>::OTF, FO = FillShape<TPF>::FOPT,
                   PP = FillShape<TPF>::PPT, CAP = FillShape<TPF>::CAP;
     __shared__ uint2 s_lo_off[OTF + 1];
@@ -714,7 +780,7 @@ __global__ __launch_bounds__(FB, 2 * LIME_FILL_WGS) void k_fill(FillArgs fa, int
     int64_t t = dev::uni64(s_tile);
     uint64_t hsum = 0, hxor = 0;
     TileRegs<TPF> R;
-    tile_load<TPF>(fa, t, R, toff, win, tseg);
+    tile_load<TPF>(fa, t, R, toff, win, tseg, tpk);
     while (true) {
         const int st = tile_stream(fa, t);
         const StreamArgs sa = st ? fa.s[1] : fa.s[0];
@@ -728,12 +794,22 @@ __global__ __launch_bounds__(FB, 2 * LIME_FILL_WGS) void k_fill(FillArgs fa, int
 #pragma unroll
         for (int k = 0; k < FO; ++k) {
             const int q = threadIdx.x * FO + k;
+            // the owner's (lo, off, gs, ge): a packed tile's two words hold
+            // them relative to its window start and its first owner's start
+            uint32_t lo = R.w0[k], off = R.w1[k], og = R.og[k], oe = R.oe[k];
+            if (LIME_FILL_PACK && R.pk) {  // (uniform)
+                lo = R.wown + (R.w0[k] >> PK_OFF_BITS);
+                off = R.w0[k] & ((1u << PK_OFF_BITS) - 1u);
+                og = R.g0 + (R.w1[k] >> PK_W_BITS);
+                oe = og + (R.w1[k] & ((1u << PK_W_BITS) - 1u));
+            }
+            off += R.add;
             if (q < nown) {
                 const uint32_t sg =
-                    R.seg != 0xffffffffu ? R.seg : contig_off(fa.off, fa.n_contigs, R.og[k]);
-                s_own[q] = u32x4{R.og[k], R.oe[k], R.orw[k], sg};
+                    R.seg != 0xffffffffu ? R.seg : contig_off(fa.off, fa.n_contigs, og);
+                s_own[q] = u32x4{og, oe, R.orw[k], sg};
             }
-            s_lo_off[q] = make_uint2(R.lo[k], q < nown ? R.off[k] : ttot);
+            s_lo_off[q] = make_uint2(q < nown ? lo : 0u, q < nown ? off : ttot);
         }
         if (threadIdx.x == 0) s_lo_off[OTF] = make_uint2(0u, ttot);
         const uint32_t wlo = R.wlo, whi = R.whi;
@@ -749,7 +825,7 @@ __global__ __launch_bounds__(FB, 2 * LIME_FILL_WGS) void k_fill(FillArgs fa, int
         // ---- prefetch the next commit (its loads overlap this one's stores)
         // (R.tnext = toff[tn]: no table read)
         const bool more = tn < fa.ntiles && (int64_t)R.tnext < oend;
-        if (more) tile_load<TPF>(fa, tn, R, toff, win, tseg);
+        if (more) tile_load<TPF>(fa, tn, R, toff, win, tseg, tpk);
         // ---- this commit's slice of the output window, in granules dealt
         // round-robin to the waves (wave w: granules w, w + FW, ...).  The
         // default granule is one equal chunk per wave: 2048-record granules
@@ -958,6 +1034,7 @@ FillArgs fill_args(PairsPlan *pl) {
     fa.toff = pl->toff;
     fa.win = pl->win;
     fa.tseg = pl->tseg;
+    fa.tpk = pl->tpk;
     fa.total = pl->total;
     fa.ntiles = pl->nt0 + pl->nt1;
     fa.off = pl->A->d_off;
@@ -990,16 +1067,16 @@ template <int TPF>
 void launch_k_fill(lime_ctx *ctx, dim3 g, const FillArgs &fa, int64_t per, bool cksum, bool win) {
     if (cksum && win)
         hipLaunchKernelGGL((k_fill<TPF, true, true>), g, dim3(FB), 0, S(ctx), fa, per, (int64_t)GR,
-                           fa.toff, fa.win, fa.tseg);
+                           fa.toff, fa.win, fa.tseg, fa.tpk);
     else if (cksum)
         hipLaunchKernelGGL((k_fill<TPF, true, false>), g, dim3(FB), 0, S(ctx), fa, per, (int64_t)GR,
-                           fa.toff, fa.win, fa.tseg);
+                           fa.toff, fa.win, fa.tseg, fa.tpk);
     else if (win)
         hipLaunchKernelGGL((k_fill<TPF, false, true>), g, dim3(FB), 0, S(ctx), fa, per, (int64_t)GR,
-                           fa.toff, fa.win, fa.tseg);
+                           fa.toff, fa.win, fa.tseg, fa.tpk);
     else
         hipLaunchKernelGGL((k_fill<TPF, false, false>), g, dim3(FB), 0, S(ctx), fa, per,
-                           (int64_t)GR, fa.toff, fa.win, fa.tseg);
+                           (int64_t)GR, fa.toff, fa.win, fa.tseg, fa.tpk);
 }
 
 int launch_fill(PairsPlan *pl, int64_t first, int64_t count, u32x4 *out, uint64_t *cksum) {
@@ -1089,11 +1166,17 @@ int intersect_plan(lime_ctx *ctx, const lime_set *A, const lime_set *B, int64_t 
     LIME_TRY(alloc(ctx, &pl->toff, (size_t)nt));
     LIME_TRY(alloc(ctx, &pl->win, (size_t)2 * nt));
     LIME_TRY(alloc(ctx, &pl->tseg, (size_t)nt));
+    LIME_TRY(alloc(ctx, &pl->tpk, (size_t)2 * (nt > 0 ? nt : 1)));
     LIME_TRY(tcnt.alloc(ctx, (size_t)nt));
     LIME_TRY(total.alloc(ctx, 2));
     // total[1]: overflow flag of the u32 tile-local offsets
     uint32_t *oflow = reinterpret_cast<uint32_t *>(total + 1);
     LIME_HIP(hipMemsetAsync(total + 1, 0, sizeof(uint64_t), S(ctx)));
+    // only k_count<false, true> writes the tiles' forms: an empty or a
+    // filtered plan has none packed
+    if (pl->filtered || A->n == 0 || B->n == 0)
+        LIME_HIP(hipMemsetAsync(pl->tpk, 0, sizeof(uint32_t) * 2 * (size_t)(nt > 0 ? nt : 1),
+                                S(ctx)));
     if (A->n > 0 && B->n > 0) {
         for (int st = 0; st < 2; ++st) {
             const lime_set *O = st == 0 ? A : B;
@@ -1111,11 +1194,11 @@ int intersect_plan(lime_ctx *ctx, const lime_set *A, const lime_set *B, int64_t 
             if (pl->filtered)
                 hipLaunchKernelGGL((k_count<true, false>), dim3((unsigned)ntl), dim3(IB), 0, S(ctx), sa,
                                    pl->tp, threshold, (const uint32_t *)pl->win, pl->olo, pl->ocnt,
-                                   tcnt, oflow);
+                                   tcnt, oflow, (uint32_t *)nullptr, 0);
             else
                 hipLaunchKernelGGL((k_count<false, true>), dim3((unsigned)ntl), dim3(IB), 0, S(ctx), sa,
                                    pl->tp, threshold, (const uint32_t *)pl->win, pl->olo, pl->ocnt,
-                                   tcnt, oflow);
+                                   tcnt, oflow, pl->tpk, A_out == nullptr ? 1 : 0);
             LIME_HIP(hipGetLastError());
         }
     } else {
@@ -1158,7 +1241,8 @@ int owner_ranges(lime_ctx *ctx, const lime_set *O, const lime_set *P, int st, in
     launch_windows(ctx, sa, tp, ntl, (int64_t)O->max_width, win, nullptr, 0, nullptr);
     hipLaunchKernelGGL((k_count<false, false>), dim3((unsigned)ntl), dim3(IB), 0, S(ctx), sa, tp,
                        threshold,
-                       (const uint32_t *)win, olo, ocnt, tcnt, (uint32_t *)nullptr);
+                       (const uint32_t *)win, olo, ocnt, tcnt, (uint32_t *)nullptr,
+                       (uint32_t *)nullptr, 0);
     LIME_HIP(hipGetLastError());
     return LIME_OK;
 }

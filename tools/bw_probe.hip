@@ -118,6 +118,9 @@ __global__ __launch_bounds__(512) void k_store_fillshape(u32x4 *out, long n, lon
 // LOADER (with L = 3) is the alternative structure: the wave past the store
 // waves fetches the next tile's words itself, with 16-B loads, into a second
 // LDS image, and the store waves never load; one barrier per tile.
+// PW: the staging words read per tile, the first PW of the tile's P_WORDS
+// (the image's planes past them stay zero): the slope of the fill's time in
+// its staging bytes, at the structure of level 3.
 // The input words are all zero at run time (the compiler cannot know), so
 // the image's offsets stay q * 82 and every LDS index stays in range.
 constexpr int P_OWN = 1024, P_PAR = 2048, P_WORDS = 5 * P_OWN + 3 * P_PAR, P_PPO = 82;
@@ -127,14 +130,22 @@ struct ProbeImage {
     u32x4 par[P_PAR];
 };
 
-template <int NT, int NSW, int L, bool LOADER>
+template <int NT, int NSW, int L, bool LOADER, int PW = P_WORDS>
 __global__ __launch_bounds__(NT) void k_store_fillgap(u32x4 *out, long n, long per,
                                                       const unsigned *__restrict__ in,
                                                       long in_tiles) {
     constexpr long T = (long)P_OWN * P_PPO + 32;  // 84000
-    constexpr int NR = P_WORDS / NT;               // staging words per thread
-    static_assert(P_WORDS % NT == 0, "staging words divide over the threads");
+    constexpr int NR = PW / NT;                    // staging words per thread
+    static_assert(PW % NT == 0, "staging words divide over the threads");
+    // (the offsets' planes, words 0 .. 2 P_OWN, keep the LDS indices in range)
+    static_assert(PW >= 2 * P_OWN && PW <= P_WORDS && (!LOADER || PW == P_WORDS),
+                  "a shorter staging read keeps the lo / off planes; the loader reads it all");
     __shared__ ProbeImage img[LOADER ? 2 : 1];
+    if (PW < P_WORDS) {
+        for (int i = threadIdx.x; i < (int)(sizeof(ProbeImage) / 4); i += NT)
+            ((unsigned *)&img[0])[i] = 0u;
+        __syncthreads();
+    }
     const long b0 = (long)blockIdx.x * per;
     const long b1 = b0 + per < n ? b0 + per : n;
     const int w = threadIdx.x / 64, lane = threadIdx.x & 63;
@@ -373,6 +384,18 @@ int main(int argc, char **argv) {
         GAP("a_prefetch", 512, 8, 1, false)
         GAP("ab_image", 512, 8, 2, false)
         GAP("abc_ldsreads", 512, 8, 3, false)
+        // (c) again at fewer staging words per tile
+#define GAPW(NAME, PW)                                                                        \
+    {                                                                                         \
+        const unsigned g = 256 * 2;                                                           \
+        const long per = (n + g - 1) / g;                                                     \
+        timeit("fillgap_" NAME, n, n * 16.0, [&] {                                            \
+            hipLaunchKernelGGL((k_store_fillgap<512, 8, 3, false, PW>), dim3(g), dim3(512), 0, \
+                               0, out, n, per, stage, in_tiles);                              \
+        });                                                                                   \
+    }
+        GAPW("abc_ldsreads_w8192", 8192)
+        GAPW("abc_ldsreads_w6144", 6144)
         GAP("abcd_wg1024", 1024, 16, 3, false)
         GAP("abcde_15of16", 1024, 15, 3, false)
         // the pure store stream in the two candidate layouts, and the
